@@ -17,6 +17,13 @@ Launch:  python bench.py [--gpus N --steps K --warmup W]   (N > 1: starts N rank
          python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...    (the driver's form)
 Each rank owns 65,536 envs with global ids rank*65536 + i (weak scaling); there is no collective
 on the data path, only a barrier and a MAX-reduce of the wall time.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (the figures the timed region itself
+gives; everything measured by a run of its own is null).  --full adds those runs: the isolated-launch time and the
+replay spread of the roofline block, the secondary lines (K-step rollout, config-5 PPO rollout and training, fp32
+storage, sample_time = 0.05, MIXED, config 2) and the two CPU baselines; --no-rollout, --no-main05 and
+--no-cpu-baseline take parts of them away again.  --dump-outputs DIR writes what the last timed step returned
+(obs, reward, done and the info tensors) as DIR/<name>.npy; inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -451,6 +458,43 @@ def check_world(args, world):
                          f"`python bench.py --gpus N` or torch.distributed.run --nproc-per-node N ... --gpus N")
 
 
+def emit(obj):
+    """One JSON line in ONE write: print() hands the text and the newline to an unbuffered stdout separately, and the
+    lines of ranks that share the launcher's stdout then run into each other."""
+    sys.stdout.write(json.dumps(obj) + "\n")
+    sys.stdout.flush()
+
+
+def step_outputs(returned):
+    """What the last ControllerEnv.step call returned -- (obs, reward, done, info) -- cloned on the device (they are the
+    env's own buffers, rewritten by the next step)."""
+    obs, reward, done, info = returned
+    out = {"obs": obs, "reward": reward, "done": done}
+    out.update(info)
+    return {k: v.clone() for k, v in out.items()}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs, rank):
+    """path/<name>.npy (rank r > 0: <name>.rank<r>.npy) per output, float64 where the tensor is, float32 otherwise
+    (done 0/1, episode_length < 2^24: exact).  Past 64 MB in all, every array keeps a fixed seeded sample of its
+    rows (the same rows of every array, sorted), and rows.npy names them."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().cpu().numpy() for k, v in outputs.items()}
+    arrs = {k: a.astype(np.float64 if a.dtype == np.float64 else np.float32) for k, a in arrs.items()}
+    n = next(iter(arrs.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in arrs.values()) + 8
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}.npy" if rank == 0 else f"{k}.rank{rank}.npy"), a)
+
+
 def binder_note(valu_frac, sq, src):
     """What the committed SQ counters (tools/pmc_summary.py) say binds the per-step kernel, or None."""
     if not sq or not sq.get("SQ_WAVE_CYCLES"):
@@ -486,6 +530,11 @@ def main():
     ap.add_argument("--variant", default="fast", choices=["fast", "faithful", "mixed"],
                     help="fast (default): identities for sin/cos/pow; faithful: the DLL's operation order; mixed: fast "
                          "with the flight aerodynamics in fp32 (tests/test_gpu_mixed.py gates)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything that takes runs of its own: isolated-launch "
+                         "time and replay spread, the secondary lines and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, reward, done, info tensors) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL over xGMI) for real runs")
     ap.add_argument("--no-rollout", action="store_true",
@@ -509,8 +558,8 @@ def main():
         t = torch.ones(1)
         if world > 1:
             tdist.all_reduce(t)
-        print(json.dumps({"rank": int(os.environ.get("RANK", "0")), "world": world,
-                          "ranks_seen": tdist.get_world_size() if world > 1 else 1, "all_reduce": float(t)}), flush=True)
+        emit({"rank": int(os.environ.get("RANK", "0")), "world": world,
+              "ranks_seen": tdist.get_world_size() if world > 1 else 1, "all_reduce": float(t)})
         if world > 1:
             tdist.destroy_process_group()
         return
@@ -548,7 +597,7 @@ def main():
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, stream=s):
             for t in range(args.steps):
-                env.step(actions[args.warmup + t])
+                returned = env.step(actions[args.warmup + t])
         torch.cuda.synchronize()
 
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -566,7 +615,7 @@ def main():
         graph.replay()
     else:
         for t in range(args.steps):
-            env.step(actions[args.warmup + t])
+            returned = env.step(actions[args.warmup + t])
     ev1.record()
     torch.cuda.synchronize()
     # each rank's clock stops when its own K steps have drained; the closing barrier (an RCCL all-reduce
@@ -579,17 +628,20 @@ def main():
     wall = reduce_max(wall, dist, device)
     region_event_us = ev0.elapsed_time(ev1) * 1e3 / args.steps   # per launch, on the launch stream
     ranks_seen = dist.get_world_size() if dist else 1
-    # two more replays of the same graph after the timed region, for the spread a single replay hides (the
+    # the last timed step's outputs, before anything below steps the env again
+    dumped = step_outputs(returned) if args.dump_outputs and args.steps > 0 else None
+    # --full: two more replays of the same graph after the timed region, for the spread a single replay hides (the
     # secondary lines report medians of such replays); `value` stays the one timed region above
-    spread = [round(d / args.steps * 1e6, 3) for d in timed_replays(graph.replay, 2)] if graph is not None else None
+    spread = [round(d / args.steps * 1e6, 3) for d in timed_replays(graph.replay, 2)] \
+        if args.full and graph is not None else None
 
     if not torch.isfinite(env.obs).all() or not torch.isfinite(env.reward).all():
         raise RuntimeError("non-finite obs/reward after the timed region")
     region_us = wall / args.steps * 1e6          # per launch incl. the launch-to-launch gap
     kern_us = region_event_us                    # HIP events over the timed region / K
-    iso_us = isolated_launch_us(env, actions)
+    iso_us = isolated_launch_us(env, actions) if args.full else None
     # the secondary lines are per-GPU figures: measured at N = 1 only, so that a multi-rank run stays short
-    secondary = not args.no_rollout and world == 1
+    secondary = args.full and not args.no_rollout and world == 1
     roll = rollout_rate(env) if secondary else None
     ppo = ppo_rollout_rate(args.envs, rank, x_f64, device, args.variant) if secondary else None
     x32 = storage_f32_rate(args.envs, rank, device, args.variant) if secondary and x_f64 else None
@@ -644,7 +696,8 @@ def main():
                      "bytes_per_env_step_stored": stored,
                      "traffic_over_algorithmic": round(traffic / (algo * args.envs), 3) if traffic else None,
                      "kernel_avg_us": round(kern_us, 3), "launch_period_us": round(region_us, 3),
-                     "isolated_launch_us": round(iso_us, 3), "replays_after_us_per_step": spread,
+                     "isolated_launch_us": round(iso_us, 3) if iso_us is not None else None,
+                     "replays_after_us_per_step": spread,
                      "valu_issue_frac": valu_frac,
                      "binder": binder_note(valu_frac, sq, sq_src),
                      "floor_us": budget_floor() if args.envs == ENVS_PER_GPU and x_f64 and args.variant == "fast" else None},
@@ -656,14 +709,16 @@ def main():
         "variant_mixed": mixed,
         "config2": cfg2,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped, rank)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         for key, fn in (("cpu_baseline", cpu_baseline), ("cpu_baseline_batched", cpu_baseline_batched)):
             try:
                 out[key] = fn() | cpu_info()
             except Exception as e:  # report, never hide
                 out[key] = {"value": None, "error": repr(e)}
     if rank == 0:
-        print(json.dumps(out), flush=True)
+        emit(out)
     if dist:
         dist.destroy_process_group()
 

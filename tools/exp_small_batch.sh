@@ -7,7 +7,7 @@ for n in ${SIZES:-4096 16384}; do
 for so in ${AB_DIR:-tools/ab}/*.so; do
   tag=$(basename $so .so)
   export B747_LIB_PATH=$(realpath $so)
-  timeout -k 10 200 python3 -u bench.py --envs $n --no-cpu-baseline --no-main05 --steps 100 > $O/$tag.$n.json 2> $O/$tag.$n.err || { echo "$tag $n failed"; tail -3 $O/$tag.$n.err; exit 1; }
+  timeout -k 10 200 python3 -u bench.py --full --envs $n --no-cpu-baseline --no-main05 --steps 100 > $O/$tag.$n.json 2> $O/$tag.$n.err || { echo "$tag $n failed"; tail -3 $O/$tag.$n.err; exit 1; }
   python3 - $O/$tag.$n.json $tag $n <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,8 +7,8 @@ timeout -k 10 900 python -u -m pytest -v --timeout 300 --timeout-method thread -
 echo "pytest rc=$rc"; grep -E "passed|failed" $O/pytest_gpu.log | tail -3
 grep -E "FAILED|Error" $O/pytest_gpu.log | head -10
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err || { tail -5 $O/bench_driver_args.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err || { tail -5 $O/bench_driver_args.err; exit 1; }
 timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_2ranks_gloo.json 2> $O/bench_2ranks_gloo.err || { tail -5 $O/bench_2ranks_gloo.err; exit 1; }
 python3 -c "
 import json
