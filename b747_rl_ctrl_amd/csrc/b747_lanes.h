@@ -344,15 +344,19 @@ __device__ __forceinline__ void env_store(const b747_env_batch &b, const EnvCfg 
 
 // Where an episode ends: the VecMonitor info (ep_final_*) and the device-side episode accumulators
 // (ep_stats, include/b747.h).  Runs on done lanes only, so the per-step path pays nothing for it.
-__device__ __forceinline__ void record_episode_end(const b747_env_batch &b, int64_t i, const EnvLane &L)
+__device__ __forceinline__ void record_episode_end(const b747_env_batch &b, int64_t i, double ep_ret, int32_t ep_len)
 {
-    if (b.ep_final_return) b.ep_final_return[i] = L.s.ep_ret;
-    if (b.ep_final_len) b.ep_final_len[i] = L.s.ep_len;
+    if (b.ep_final_return) b.ep_final_return[i] = ep_ret;
+    if (b.ep_final_len) b.ep_final_len[i] = ep_len;
     if (b.ep_stats) {
         b.ep_stats[i] += 1.0;
-        b.ep_stats[b.n + i] += L.s.ep_ret;
-        b.ep_stats[2 * b.n + i] += (double)L.s.ep_len;
+        b.ep_stats[b.n + i] += ep_ret;
+        b.ep_stats[2 * b.n + i] += (double)ep_len;
     }
+}
+__device__ __forceinline__ void record_episode_end(const b747_env_batch &b, int64_t i, const EnvLane &L)
+{
+    record_episode_end(b, i, L.s.ep_ret, L.s.ep_len);
 }
 
 // Controller.reset + Model.initialize (core/controller.py:134-201, core/model.py:238-244)

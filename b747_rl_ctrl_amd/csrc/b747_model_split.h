@@ -44,7 +44,8 @@ __device__ __forceinline__ void ms_prologue_barrier()
 }
 
 // The flight side's exported signals of the stage-4 pass (b747::pass's read-out): its pass and the stage input's X0,
-// h, Vx, Vy, w (the control side writes its 18 in place: as a helper they cost the K-step kernel 68 B of scratch)
+// h, Vx, Vy, w (the control side writes its 18 in place, in both kernels: as a helper -- taking the pass by reference or
+// every value as a scalar alike -- they cost the K-step fp64 kernel 68 B of scratch, tests/test_kernel_resources.py)
 __device__ __forceinline__ void ms_flight_signals(double *sig, int64_t n, int64_t i, const FlightPass &fp, double x0,
                                                   double h, double vx, double vy, double w)
 {
@@ -84,7 +85,6 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_step_split(b747
     XT *Xw = (XT *)b.X;
     double *sig = b.sig;
     const double temp = 0.5 * H;
-    const double t6 = H / 6.0;
 
     if (role == 0) {
         // ---- flight wave (k_env_step_split's, with the pass's flight-side signals at stage 4)
@@ -105,16 +105,10 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_step_split(b747
         unsigned seen_ah = 0u, seen_dl = 0u;
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
-            int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" : "+s"(zoff));
-#endif
+            const int zoff = opaque_zoff();
             if (st > 0) {
                 pair_wait_seen(&c_ah[0], (unsigned)st, seen_ah);
-                a.sth = xa[st - 1][0][el]; a.cth = xa[st - 1][1][el]; a.h = xa[st - 1][2][el];
-                a.inva = xa[st - 1][3][el]; a.rho = xa[st - 1][4][el];
-                a.q0n = xa[st - 1][5][el]; a.q3n = xa[st - 1][6][el];
-                a.iDC0 = xai[st - 1][el];
+                ahead_get(xa[st - 1], xai[st - 1], el, a);
             }
             FlightPass fp{};
             flight_pre<false>(x, tb + zoff, split_kfit(zoff), km, fp, fk, a);
@@ -123,13 +117,7 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_step_split(b747
             flight_post(x, xdl[st][el], fp, dX, fk);
             if (st == 3 && sig && valid)                        // the stage-4 read-out
                 ms_flight_signals(sig, n, i, fp, x[0], x[1], x[4], x[5], x[6]);
-            const double c = (st == 2) ? H : temp;              // RK4 combine (b747::major_step, dll@0x2c60)
-            const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
-#pragma unroll
-            for (int j = 0; j < kNF; ++j) {
-                acc[j] = acc[j] + wm * dX[j];
-                x[j] = c * dX[j] + y[j];
-            }
+            rk4_stage<kNF>(st, dX, x, y, acc);
             if (st < 2) {
                 xp[st][0][el] = x[5];
                 xp[st][1][el] = x[6];
@@ -138,7 +126,7 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_step_split(b747
         }
         if (valid) {
 #pragma unroll
-            for (int j = 0; j < kNF; ++j) st_state(&Xw[kFX[j] * n + i], (XT)(acc[j] * t6 + y[j]));
+            for (int j = 0; j < kNF; ++j) st_state(&Xw[kFX[j] * n + i], (XT)rk4_end(acc[j], y[j]));
         }
         return;
     }
@@ -155,12 +143,9 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_step_split(b747
         const double yq[3] = {xq[0], xq[1], xq[2]};
         FlightAhead at;
         pitch_attitude(xq[1], xq[2], fk, at);
-        xa0[0][el] = at.sth; xa0[1][el] = at.cth; xa0[2][el] = xq[0];
+        att_put(xa0, el, at.sth, at.cth, xq[0]);
         pair_post(&c_a0[0], 1u);
-        int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+s"(zoff));
-#endif
+        const int zoff = opaque_zoff();
 #pragma unroll
         for (int st = 0; st < 3; ++st) {
             if (st > 0) {
@@ -169,13 +154,10 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_step_split(b747
                 w = xp[st - 1][1][el];
             }
             const double dq[3] = {vy, dq0_of(w, at.q3n), dq3_of(w, at.q0n)};
-            const double c = (st == 2) ? H : temp;
 #pragma unroll
-            for (int q = 0; q < 3; ++q) xq[q] = c * dq[q] + yq[q];
+            for (int q = 0; q < 3; ++q) xq[q] = rk4_c(st) * dq[q] + yq[q];
             at = flight_ahead<false>(xq[1], xq[2], xq[0], split_kfit(zoff), fk);
-            xa[st][0][el] = at.sth; xa[st][1][el] = at.cth; xa[st][2][el] = at.h;
-            xa[st][3][el] = at.inva; xa[st][4][el] = at.rho; xa[st][5][el] = at.q0n; xa[st][6][el] = at.q3n;
-            xai[st][el] = at.iDC0;
+            ahead_put(xa[st], xai[st], el, at);
             pair_post(&c_ah[0], (unsigned)st + 1u);
         }
         return;
@@ -231,17 +213,11 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_step_split(b747
     {
         unsigned seen_a0 = 0u;
         pair_wait_seen(&c_a0[0], 1u, seen_a0);
-        att[0].sth = xa0[0][el];
-        att[0].cth = xa0[1][el];
-        hst[0] = xa0[2][el];
+        att_get(xa0, el, att[0].sth, att[0].cth, hst[0]);
     }
     Params P{};
     P.deltaz = deltaz; P.vartheta = vartheta; P.h_zh = h_zh; P.flags = flags;
-    PassRef R{};
-    R.has_ref = (k != 0u);
-    R.t_ref = R.has_ref ? t_of(k - 1u) : 0.0;
-    R.e_ref = D.e_prev; R.ed_ref = D.ed_prev; R.rl_prevY = D.rl_prevY;
-    R.y_dss = D.y_dss; R.mem = mem;
+    PassRef R = pass_ref_at(k, D, mem);
 #pragma unroll
     for (int j = 0; j < kNC; ++j) { y[j] = x[j]; acc[j] = 0.0; }
     PassOut o{};
@@ -276,14 +252,8 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_step_split(b747
             sig[S_U_COM_PID * n + i] = o.UPID;
             sig[S_VARTHETA_ZH * n + i] = thPID;
         }
-        if (st == 0) {   // MAJOR-only updates (dll@0x271a), then only what the step changed is written back
-            D.x_dss = dss_hit ? B747_DSS_A * D.x_dss + B747_DSS_B * ud : D.x_dss;
-            D.rl_prevY = o.r;
-            D.e_prev = o.e;
-            D.ed_prev = o.ed;
-            mem = o.and3_bits;
-            R.has_ref = true; R.t_ref = tk; R.e_ref = o.e; R.ed_ref = o.ed; R.rl_prevY = o.r;
-            R.mem = mem_held;
+        if (st == 0) {   // MAJOR-only updates, then only what the step changed is written back
+            major_update(D, mem, R, o, dss_hit, ud, tk, mem_held);
             if (valid) {
                 if (dss_hit) {
                     st_state(&b.disc[0 * n + i], D.x_dss);
@@ -297,31 +267,20 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_step_split(b747
                 b.mem[i] = (uint8_t)mem;
             }
         }
-        const double c = (st == 2) ? H : temp;
-        const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
-#pragma unroll
-        for (int j = 0; j < kNC; ++j) {
-            acc[j] = acc[j] + wm * dX[j];
-            x[j] = c * dX[j] + y[j];
-        }
+        rk4_stage<kNC>(st, dX, x, y, acc);
     };
-    int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+s"(zoff));
-#endif
+    const int zoff = opaque_zoff();
     cstage(0, zoff);
     unsigned seen_ah = 0u;
 #pragma unroll
     for (int st = 1; st < 4; ++st) {
         pair_wait_seen(&c_ah[0], (unsigned)st, seen_ah);
-        att[st].sth = xa[st - 1][0][el];
-        att[st].cth = xa[st - 1][1][el];
-        hst[st] = xa[st - 1][2][el];
+        att_get(xa[st - 1], el, att[st].sth, att[st].cth, hst[st]);
         cstage(st, zoff);
     }
     if (valid) {
 #pragma unroll
-        for (int j = 0; j < kNC; ++j) st_state(&Xw[(9 + j) * n + i], (XT)(acc[j] * t6 + y[j]));
+        for (int j = 0; j < kNC; ++j) st_state(&Xw[(9 + j) * n + i], (XT)rk4_end(acc[j], y[j]));
     }
 }
 
@@ -363,7 +322,6 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_steps_split(b74
     double *sig = b.sig;
     const unsigned G = 4u * (unsigned)n_steps;      // stages of the launch
     const double temp = 0.5 * H;
-    const double t6 = H / 6.0;
 
     if (role == 0) {
         // ---- flight wave
@@ -386,19 +344,14 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_steps_split(b74
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
                 const unsigned g = 4u * s + (unsigned)st;
-                int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-                asm volatile("" : "+s"(zoff));
-#endif
+                const int zoff = opaque_zoff();
                 FlightAhead a;
                 if (g == 0u) {
                     a = flight_ahead<false>(x, split_kfit(zoff), fk);   // the launch's first stage: its own
                 } else {
                     pair_wait_seen(&c_ah[0], g + 1u, seen_ah);
                     const int r = (int)(g % (unsigned)kMkRA);
-                    a.sth = xa[r][0][el]; a.cth = xa[r][1][el]; a.h = xa[r][2][el];
-                    a.inva = xa[r][3][el]; a.rho = xa[r][4][el]; a.q0n = xa[r][5][el]; a.q3n = xa[r][6][el];
-                    a.iDC0 = xai[r][el];
+                    ahead_get(xa[r], xai[r], el, a);
                 }
                 FlightPass fp{};
                 flight_pre<false>(x, tb + zoff, split_kfit(zoff), km, fp, fk, a);
@@ -407,16 +360,10 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_steps_split(b74
                 flight_post(x, xdl[s % (unsigned)kMkRD][st][el], fp, dX, fk);
                 if (st == 3 && s + 1u == (unsigned)n_steps && sig && valid)   // the last step's stage-4 read-out
                     ms_flight_signals(sig, n, i, fp, x[0], x[1], x[4], x[5], x[6]);
-                const double c = (st == 2) ? H : temp;
-                const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
-#pragma unroll
-                for (int j = 0; j < kNF; ++j) {
-                    acc[j] = acc[j] + wm * dX[j];
-                    x[j] = c * dX[j] + y[j];
-                }
+                rk4_stage<kNF>(st, dX, x, y, acc);
                 if (st == 3) {                                  // the step's end state (major_step)
 #pragma unroll
-                    for (int j = 0; j < kNF; ++j) x[j] = acc[j] * t6 + y[j];
+                    for (int j = 0; j < kNF; ++j) x[j] = rk4_end(acc[j], y[j]);
                 }
                 if (g + 1u < G) {                               // (Vy, w) of stage g + 1's input, to the ahead wave
                     const int r = (int)((g + 1u) % (unsigned)kMkRP);
@@ -443,20 +390,15 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_steps_split(b74
     ms_prologue_barrier();
         const FlightK fk = flight_consts();
         unsigned seen_fl = 0u, seen_cs = 0u;
-        int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+s"(zoff));
-#endif
+        const int zoff = opaque_zoff();
         // post stage g's values: the flight ring (g >= 1) and the control ring (after the control wave has read the
         // stage kMkRC earlier from the same slot)
         auto post = [&](unsigned g, const FlightAhead &at) __attribute__((always_inline)) {
             if (g >= (unsigned)kMkRC) pair_wait_seen(&c_cs[0], g - (unsigned)kMkRC + 1u, seen_cs);
             const int rc = (int)(g % (unsigned)kMkRC);
-            xc[rc][0][el] = at.sth; xc[rc][1][el] = at.cth; xc[rc][2][el] = at.h;
+            att_put(xc[rc], el, at.sth, at.cth, at.h);
             const int ra = (int)(g % (unsigned)kMkRA);
-            xa[ra][0][el] = at.sth; xa[ra][1][el] = at.cth; xa[ra][2][el] = at.h;
-            xa[ra][3][el] = at.inva; xa[ra][4][el] = at.rho; xa[ra][5][el] = at.q0n; xa[ra][6][el] = at.q3n;
-            xai[ra][el] = at.iDC0;
+            ahead_put(xa[ra], xai[ra], el, at);
             pair_post(&c_ah[0], g + 1u);
         };
         FlightAhead at = flight_ahead<false>(xq[1], xq[2], xq[0], split_kfit(zoff), fk);
@@ -475,16 +417,10 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_steps_split(b74
                     w = xp[r][1][el];
                 }
                 const double dq[3] = {vy, dq0_of(w, at.q3n), dq3_of(w, at.q0n)};
-                const double c = (st == 2) ? H : temp;
-                const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    accq[q] = accq[q] + wm * dq[q];
-                    xq[q] = c * dq[q] + yq[q];
-                }
+                rk4_stage<3>(st, dq, xq, yq, accq);
                 if (st == 3) {
 #pragma unroll
-                    for (int q = 0; q < 3; ++q) xq[q] = accq[q] * t6 + yq[q];
+                    for (int q = 0; q < 3; ++q) xq[q] = rk4_end(accq[q], yq[q]);
                 }
                 if (g + 1u < G) {
                     at = flight_ahead<false>(xq[1], xq[2], xq[0], split_kfit(zoff), fk);
@@ -539,24 +475,18 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_steps_split(b74
         const bool dss_hit = (k % 5u) == 0u;
         const double ud = delay_out(k, D.u_hist);                // (major_step's start of step)
         D.y_dss = dss_hit ? D.x_dss * B747_DSS_C + B747_DSS_D * ud : D.y_dss;
-        PassRef R{};
-        R.has_ref = (k != 0u);
-        R.t_ref = R.has_ref ? t_of(k - 1u) : 0.0;
-        R.e_ref = D.e_prev; R.ed_ref = D.ed_prev; R.rl_prevY = D.rl_prevY;
-        R.y_dss = D.y_dss; R.mem = mem;
+        PassRef R = pass_ref_at(k, D, mem);
         const uint32_t mem_held = mem;
 #pragma unroll
         for (int j = 0; j < kNC; ++j) { y[j] = x[j]; acc[j] = 0.0; }
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
             const unsigned g = 4u * s + (unsigned)st;
-            int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" : "+s"(zoff));
-#endif
+            const int zoff = opaque_zoff();
             pair_wait_seen(&c_ah[0], g + 1u, seen_ah);
             const int rc = (int)(g % (unsigned)kMkRC);
-            const double sth = xc[rc][0][el], cth = xc[rc][1][el], h = xc[rc][2][el];
+            double sth, cth, h;
+            att_get(xc[rc], el, sth, cth, h);
             pair_post(&c_cs[0], g + 1u);                         // (slot rc read: the ahead wave may reuse it)
             const double t = (st == 0) ? tk : (st == 3 ? tnew : temp + tk);
             const double theta = unit_atan2(sth, cth, split_kfit(zoff));
@@ -600,16 +530,10 @@ __global__ __launch_bounds__(kMsBlock) B747_NO_FMAC void k_model_steps_split(b74
                 // command out of the next step's delay output)
                 if (!lock && s + 1u < (unsigned)n_steps) post_table(k + 1u, delay_out(k + 1u, D.u_hist), s + 1u);
             }
-            const double c = (st == 2) ? H : temp;
-            const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
-#pragma unroll
-            for (int j = 0; j < kNC; ++j) {
-                acc[j] = acc[j] + wm * dX[j];
-                x[j] = c * dX[j] + y[j];
-            }
+            rk4_stage<kNC>(st, dX, x, y, acc);
         }
 #pragma unroll
-        for (int j = 0; j < kNC; ++j) x[j] = acc[j] * t6 + y[j];
+        for (int j = 0; j < kNC; ++j) x[j] = rk4_end(acc[j], y[j]);
         k += 1u;
     }
     if (valid) {

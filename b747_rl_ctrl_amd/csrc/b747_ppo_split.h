@@ -272,17 +272,6 @@ __global__ __launch_bounds__(2 * ENVS) B747_NO_FMAC void k_rollout_split(b747_en
     bool any_reset_env = false, done = false, pair_reset = false;
     float r = 0.0f;
     double deltaz = 0.0, vartheta = 0.0, upid = 0.0;
-    // record_episode_end (flight)
-    // (the step's opaque copy of i: addresses derived from i itself are hoisted out of the loop and spilled)
-    auto record_end = [&](int32_t ep_len, int64_t ie) __attribute__((always_inline)) {
-        if (b.ep_final_return) b.ep_final_return[ie] = ep_ret;
-        if (b.ep_final_len) b.ep_final_len[ie] = ep_len;
-        if (b.ep_stats) {
-            b.ep_stats[ie] += 1.0;
-            b.ep_stats[n + ie] += ep_ret;
-            b.ep_stats[2 * n + ie] += (double)ep_len;
-        }
-    };
     const float log_std = POLICY ? w[PD.log_std] : 0.0f;
     const float sdev = expf(log_std);
     uint64_t ctr0 = (POLICY && ra.step_base) ? *ra.step_base : 0u;
@@ -291,7 +280,6 @@ __global__ __launch_bounds__(2 * ENVS) B747_NO_FMAC void k_rollout_split(b747_en
     float a_in = 0.0f;                                  // !POLICY: this step's action (prefetched one step ahead)
     if (!POLICY && !flight && T > 0) a_in = ra.actions[il];
     const FlightK fk = flight_consts();
-    const double t6 = H / 6.0;
 
     for (int32_t t = 0; t < T; ++t) {
         int64_t iv = i, ilv = il;
@@ -334,20 +322,11 @@ __global__ __launch_bounds__(2 * ENVS) B747_NO_FMAC void k_rollout_split(b747_en
                     if (lock) pair_wait<0>(&c_dl[wv], 4u * u + (unsigned)st + 1u);
                     double dX[kNF];
                     flight_post(x, xdl[par][st][el], fp, dX, fk);
-                    const double c = (st == 2) ? H : 0.5 * H;
-                    const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
-#pragma unroll
-                    for (int j = 0; j < kNF; ++j) {
-                        acc[j] = acc[j] + wm * dX[j];
-                        x[j] = c * dX[j] + y[j];
-                    }
+                    rk4_stage<kNF>(st, dX, x, y, acc);
                 };
 #pragma unroll
                 for (int st = 0; st < 4; ++st) {
-                    int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-                    asm volatile("" : "+s"(zoff));
-#endif
+                    const int zoff = opaque_zoff();
                     if (st > 0) post(st - 1);
                     const FlightAhead a = flight_ahead<MIX, kSkipStrat>(x, split_kfit(zoff), fk);
                     xth[st][el] = unit_atan2(a.sth, a.cth, split_kfit(zoff));   // theta itself (off the control's chain)
@@ -358,7 +337,7 @@ __global__ __launch_bounds__(2 * ENVS) B747_NO_FMAC void k_rollout_split(b747_en
                 }
                 post(3);
 #pragma unroll
-                for (int j = 0; j < kNF; ++j) x[j] = (SUB && !act) ? y[j] : acc[j] * t6 + y[j];
+                for (int j = 0; j < kNF; ++j) x[j] = (SUB && !act) ? y[j] : rk4_end(acc[j], y[j]);
             }
             // ---- read-out of step t (EnvReadOut of the kind-3 configuration): obs_{t+1} to the policy.  The control
             // wave rewrites xcv / xcu only after this wave's next stage-0 post, so they are read here in any order.
@@ -400,7 +379,8 @@ __global__ __launch_bounds__(2 * ENVS) B747_NO_FMAC void k_rollout_split(b747_en
 #pragma unroll
                     for (int q = 0; q < OD; ++q) obs_buf[row * OD + q] = onew[q];
                 }
-                if (done) record_end(ep_len, iv);
+                // (the step's opaque copy of i: addresses derived from i itself are hoisted out of the loop and spilled)
+                if (done) record_episode_end(b, iv, ep_ret, ep_len);
             }
             if (valid) {
                 if (t == T - 1) {
@@ -524,19 +504,11 @@ __global__ __launch_bounds__(2 * ENVS) B747_NO_FMAC void k_rollout_split(b747_en
                 const uint32_t mem_held = mem;
                 const double ud = delay_out(k, D.u_hist);
                 D.y_dss = (dss_hit && act) ? D.x_dss * B747_DSS_C + B747_DSS_D * ud : D.y_dss;
-                PassRef R{};
-                R.has_ref = (k != 0u);
-                R.t_ref = R.has_ref ? t_of(k - 1u) : 0.0;
-                R.e_ref = D.e_prev; R.ed_ref = D.ed_prev; R.rl_prevY = D.rl_prevY;
-                R.y_dss = D.y_dss; R.mem = mem;
+                PassRef R = pass_ref_at(k, D, mem);
                 double thPID = 0.0;
 #pragma unroll
                 for (int st = 0; st < 4; ++st) {
-                    int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-                    asm volatile("" : "+s"(zoff));
-#endif
-                    (void)zoff;
+                    (void)opaque_zoff();
                     pair_wait<1>(&f_th[wv], 4u * u + (unsigned)st + 1u);
                     if (st == 0) B747_PSTAMP(4);
                     const double ts = (st == 0) ? tk : (st == 3 ? tnew : temp + tk);
@@ -551,14 +523,7 @@ __global__ __launch_bounds__(2 * ENVS) B747_NO_FMAC void k_rollout_split(b747_en
                     if (st == 3) {
                         if (s + 1u == nsub) {   // the read-out's stage-4 signals of the env step's last DLL step
                             SigVals sv;
-                            sv.v[S_SIM_TIME] = ts;
-                            sv.v[S_DVARTHETA] = po.e;
-                            sv.v[S_VARTHETA_ZH] = thPID;
-                            sv.v[S_U_COM_PID] = po.UPID;
-                            sv.v[S_DVARTHETA_DT] = po.ed;
-                            sv.v[S_DVARTHETA_DT_DT] = po.edd;
-                            sv.v[S_ITSE] = x[8];
-                            sv.v[S_DVARTHETA_INT] = x[4];
+                            readout_signals(sv, ts, po, thPID, x);
                             SigStash<kSplitSigMask>{&sg[0][el], ENVS}(sv);
                             pair_post(&c_st[wv], ut + 1u);
                         }
@@ -570,15 +535,9 @@ __global__ __launch_bounds__(2 * ENVS) B747_NO_FMAC void k_rollout_split(b747_en
                             pair_post(&c_dl[wv], u + 2u);
                         }
                     }
-                    if (st == 0) {   // MAJOR-only updates (dll@0x271a), then DLL step u + 1's delta table
-                        D.x_dss = (dss_hit && act) ? B747_DSS_A * D.x_dss + B747_DSS_B * ud : D.x_dss;
+                    if (st == 0) {   // MAJOR-only updates
+                        major_update(D, mem, R, po, dss_hit, ud, tk, mem_held, act);
                         hist_put(D.u_hist, k, act ? po.Ucom : hist_get(D.u_hist, k));
-                        D.rl_prevY = act ? po.r : D.rl_prevY;
-                        D.e_prev = act ? po.e : D.e_prev;
-                        D.ed_prev = act ? po.ed : D.ed_prev;
-                        mem = act ? po.and3_bits : mem;
-                        R.has_ref = true; R.t_ref = tk; R.e_ref = po.e; R.ed_ref = po.ed; R.rl_prevY = po.r;
-                        R.mem = mem_held;
                         if (s == 0u) {
                             // the read-out's inputs of this env step: written only now, after this DLL step's stage-0
                             // wait, i.e. after the flight wave has read the previous step's (its read-out precedes its
@@ -587,17 +546,11 @@ __global__ __launch_bounds__(2 * ENVS) B747_NO_FMAC void k_rollout_split(b747_en
                             xcu[0][el] = flags; xcu[1][el] = k_start;
                         }
                     }
-                    const double c = (st == 2) ? H : temp;
-                    const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
-#pragma unroll
-                    for (int j = 0; j < kNC; ++j) {
-                        acc[j] = acc[j] + wm * dX[j];
-                        x[j] = c * dX[j] + y[j];
-                    }
+                    rk4_stage<kNC>(st, dX, x, y, acc);
                     B747_PSTAMP(5 + st);
                 }
 #pragma unroll
-                for (int j = 0; j < kNC; ++j) x[j] = (SUB && !act) ? y[j] : acc[j] * t6 + y[j];
+                for (int j = 0; j < kNC; ++j) x[j] = (SUB && !act) ? y[j] : rk4_end(acc[j], y[j]);
                 k += act ? 1u : 0u;
             }
             upid = po.UPID;

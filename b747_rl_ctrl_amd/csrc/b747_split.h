@@ -1,32 +1,37 @@
-// b747_split.h -- the single-step env kernel with every env split over TWO waves (FAST, kind 3; fp64 or fp32 X storage),
-// and the flight / control pieces the two-wave K-step and PPO rollout kernels (b747_ppo_split.h) share with it.
+// b747_split.h -- the single-step env kernel with every env split over THREE waves (k_env_step_split: FAST, kind 3;
+// fp64 or fp32 X storage), and the pieces the other multi-wave kernels share with it: the flight and control passes,
+// the delta table, the pair hand-offs and the small per-stage helpers (the two-wave K-step / PPO rollout kernel,
+// b747_ppo_split.h; the three-wave model kernels, b747_model_split.h).
 //
-// Why two waves: 65,536 envs are exactly one wave per SIMD, and one wave issues at most one instruction per ~4-5
+// Why several waves: 65,536 envs are exactly one wave per SIMD, and one wave issues at most one instruction per ~4-5
 // cycles, pays ~8 cycles for an fp64 op with a scalar operand and ~11 for a dependent one (tools/ubench_valu.hip):
-// the RK4 stages of the one-wave kernel keep the VALU only about half busy (profiles/EXPERIMENTS.md).  Here a 512-thread
-// workgroup owns 256 envs and each env has a lane in two waves that share a SIMD (waves w and w + 4: measured,
-// tools/ubench_simd.hip), so every SIMD runs the flight and the control wave of the same 64 envs.
+// the RK4 stages of the one-wave kernel keep the VALU only about half busy (profiles/EXPERIMENTS.md).  Here a 768-thread
+// workgroup owns 256 envs and each env has a lane in three waves that share a SIMD (waves w, w + 4 and w + 8:
+// measured, tools/ubench_simd.hip), so every SIMD runs the flight, the ahead and the control wave of the same 64 envs
+// (small batches: 64 envs and one wave triple per workgroup, the three waves on three SIMDs of a CU).
 //
-// Round 5: the control wave LEADS (k_env_step_split).  The dependency chain of a step is the flight wave's: stage
-// s + 1's air data need stage s's forces.  Everything else reads that chain only two stages late:
+// The dependency chain of a step is the flight wave's: stage s + 1's air data need stage s's forces.  Everything
+// else reads that chain only two stages late:
 //   * the attitude (q0, q3) and altitude h of stage s + 1's input are x_s + c_s dX_s with dq_s = f(w_s, q_s) and
 //     dh_s = Vy_s -- stage s's INPUT values, which the flight wave's combine of stage s - 1 produced;
 //   * the control stage s reads theta_s and h_s, i.e. the flight wave's stage s - 2;
 //   * the read-out (observation, reward, done) reads only the control stage 3's signals.
-// So the control wave integrates h, q0 and q3 itself, evaluates the normalised attitude and the ISA atmosphere of
-// each flight stage one stage ahead and hands them over (the part of a flight stage that is not its alpha / lookup
-// chain), runs its own stages from them, and finishes the read-out while the flight wave is still in its last
-// stages.  The flight wave keeps X0, Vx, Vy and w and runs only the chain: air data, alpha, the table lookups, the
-// forces and moment, the combine, then posts (Vy, w) of the next stage's input.  Per wave pair the hand-offs are
-// LDS progress counters (pair_post / pair_wait), not workgroup barriers:
+// So the ahead wave integrates h, q0 and q3 itself, evaluates the normalised attitude and the ISA atmosphere of each
+// flight stage one stage ahead and hands them to the flight wave (the part of a flight stage that is not its alpha /
+// lookup chain) and sin / cos theta and h to the control wave, which runs its stages from them and finishes the
+// read-out and the resets while the flight wave is still in its last stages.  The flight wave keeps X0, Vx, Vy and w
+// and runs only the chain: air data, alpha, the table lookups, the forces and moment, the combine, then posts (Vy, w)
+// of the next stage's input.  Per wave triple the hand-offs are LDS progress counters (pair_post / pair_wait), not
+// workgroup barriers:
 //   flight:  stage 0 (own attitude / atmosphere) -> [delta_0] -> post (Vy, w)_1 -> [ahead_1] stage 1 -> ... stage 3
-//   control: delta table, ahead_1 -> stage 0 -> [(Vy, w)_1] ahead_2 -> stage 1 -> [(Vy, w)_2] ahead_3 -> stage 2
-//            -> stage 3 -> read-out, resets -> [(Vy, w)_3] the last combine of h, q0, q3
+//   ahead:   stage 0's sin / cos theta, h (posted) -> ahead_1 -> [(Vy, w)_1] ahead_2 -> [(Vy, w)_2] ahead_3
+//   control: delta table -> [theta_0] stage 0 -> [ahead_1] stage 1 -> [ahead_2] stage 2 -> [ahead_3] stage 3
+//            -> read-out, resets
 // The elevator delta the flight wave's moment sees is, for MANUAL control (no SS PID, no dead zone: every env of the
 // training configuration), the saturated rate-limiter output -- a function of the stage time and the discrete state
 // alone, posted up front (stage 0's first, at issue priority 3, then the other three).  A wave triple holding an env
-// whose delta depends on the pitch error of
-// the same stage (SS PID, dead zone) posts it per stage instead ("lock step", same code, one more wait per stage).
+// whose delta depends on the pitch error of the same stage (SS PID, dead zone) posts it per stage instead ("lock
+// step", same code, one more wait per stage).
 // Every expression is the one b747::pass / major_step / env_step_lane evaluate for this configuration; the FAST
 // unit's FMA contraction may fuse a different product of a sum than in the one-wave kernel (ulp-level;
 // tests/test_gpu_split.py).  Lanes past N step a copy of env N-1 and store nothing.
@@ -472,23 +477,35 @@ __device__ __forceinline__ double delay_out3(uint32_t k, const Hist3 &u)
 // SS PID or its dead zone (D: x_dss / rl_prevY after the previous step's MAJOR update, y_dss before this step's DSS
 // update; ud: the delay output of the step): the actuator at each stage time, stage 0 on the step's start state,
 // stages 1-3 after the MAJOR update (PrevY = r of stage 0 at time t_k); stages 1 and 2 share the time t_k + h/2
-__device__ __forceinline__ void delta_table(uint32_t k, const Disc &D, double ud, double *d)
+// (its two pieces, for the per-step kernel, which posts stage 0's delta before it computes the rest: the actuator's
+// reference at stage 0, and the deltas of stages 1-3 from stage 0's rate-limiter output r0)
+__device__ __forceinline__ PassRef delta_ref0(uint32_t k, const Disc &D, double ud)
 {
-    const double tk = t_of(k);
-    const double tnew = (double)(k + 1u) * H;
-    const double temp = 0.5 * H;
     const bool dss_hit = (k % 5u) == 0u;
     PassRef R{};
     R.has_ref = (k != 0u);
     R.t_ref = R.has_ref ? t_of(k - 1u) : 0.0;
     R.rl_prevY = D.rl_prevY;
     R.y_dss = dss_hit ? D.x_dss * B747_DSS_C + B747_DSS_D * ud : D.y_dss;
-    double r0, d0, r1, d1, r3, d3;
-    actuator(tk, R, r0, d0);
-    PassRef R1 = R;
+    return R;
+}
+__device__ __forceinline__ void delta_rest(uint32_t k, const PassRef &R0, double r0, double &d1, double &d3)
+{
+    const double tk = t_of(k);
+    const double tnew = (double)(k + 1u) * H;
+    const double temp = 0.5 * H;
+    PassRef R1 = R0;
     R1.has_ref = true; R1.t_ref = tk; R1.rl_prevY = r0;
+    double r1, r3;
     actuator(temp + tk, R1, r1, d1);
     actuator(tnew, R1, r3, d3);
+}
+__device__ __forceinline__ void delta_table(uint32_t k, const Disc &D, double ud, double *d)
+{
+    const PassRef R = delta_ref0(k, D, ud);
+    double r0, d0, d1, d3;
+    actuator(t_of(k), R, r0, d0);
+    delta_rest(k, R, r0, d1, d3);
     d[0] = d0; d[1] = d1; d[2] = d1; d[3] = d3;
 }
 __device__ __forceinline__ void delta_table(uint32_t k, const Disc &D, double *d)
@@ -525,6 +542,102 @@ __device__ __forceinline__ void pair_wait_seen(unsigned *f, unsigned v, unsigned
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
 }
 
+// What the ahead wave hands over per stage (a slot of the kernel's LDS array, stage- or ring-indexed): the flight
+// wave's record -- sin, cos theta, h, 1 / a, rho, q0n, q3n and the dCm altitude interval -- whose first three rows
+// are also the control wave's attitude record (its own three-row slots for stage 0 and in the K-step kernel).  The
+// caller posts after a put and waits before a get.
+constexpr int kAheadF = 7;
+template <int E>
+__device__ __forceinline__ void ahead_put(double (&xa)[kAheadF][E], int (&xai)[E], int el, const FlightAhead &at)
+{
+    xa[0][el] = at.sth; xa[1][el] = at.cth; xa[2][el] = at.h;
+    xa[3][el] = at.inva; xa[4][el] = at.rho; xa[5][el] = at.q0n; xa[6][el] = at.q3n;
+    xai[el] = at.iDC0;
+}
+template <int E>
+__device__ __forceinline__ void ahead_get(const double (&xa)[kAheadF][E], const int (&xai)[E], int el, FlightAhead &a)
+{
+    a.sth = xa[0][el]; a.cth = xa[1][el]; a.h = xa[2][el];
+    a.inva = xa[3][el]; a.rho = xa[4][el]; a.q0n = xa[5][el]; a.q3n = xa[6][el];
+    a.iDC0 = xai[el];
+    a.invaf = (float)a.inva; a.rhof = (float)a.rho;   // (MIX: exactly the fp32 values)
+}
+template <int R, int E>
+__device__ __forceinline__ void att_put(double (&xc)[R][E], int el, double sth, double cth, double h)
+{
+    xc[0][el] = sth; xc[1][el] = cth; xc[2][el] = h;
+}
+template <int R, int E>
+__device__ __forceinline__ void att_get(const double (&xc)[R][E], int el, double &sth, double &cth, double &h)
+{
+    sth = xc[0][el]; cth = xc[1][el]; h = xc[2][el];
+}
+
+// ------------------------------------------------------------ pieces every split kernel's roles use ----
+// as major_step: each stage re-derives its constant pointers from an offset the compiler cannot see through
+__device__ __forceinline__ int opaque_zoff()
+{
+    int zoff = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(zoff));
+#endif
+    return zoff;
+}
+
+// RK4 (b747::major_step, dll@0x2c60): stage st's derivatives into the accumulator and the next stage's input; the
+// step's end value
+__device__ __forceinline__ double rk4_c(int st) { return (st == 2) ? H : 0.5 * H; }
+template <int N>
+__device__ __forceinline__ void rk4_stage(int st, const double *dX, double *x, const double *y, double *acc)
+{
+    const double c = rk4_c(st);
+    const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        acc[j] = acc[j] + wm * dX[j];
+        x[j] = c * dX[j] + y[j];
+    }
+}
+__device__ __forceinline__ double rk4_end(double acc, double y) { return acc * (H / 6.0) + y; }
+
+// The control passes' reference at the start of the step at counter k (D after the step's DSS update)
+__device__ __forceinline__ PassRef pass_ref_at(uint32_t k, const Disc &D, uint32_t mem)
+{
+    PassRef R{};
+    R.has_ref = (k != 0u);
+    R.t_ref = R.has_ref ? t_of(k - 1u) : 0.0;
+    R.e_ref = D.e_prev; R.ed_ref = D.ed_prev; R.rl_prevY = D.rl_prevY;
+    R.y_dss = D.y_dss; R.mem = mem;
+    return R;
+}
+// MAJOR-only updates (dll@0x271a) after the stage-0 pass, the register part (the U_com history and the stores are the
+// kernel's): ud the step's delay output, mem_held the anti-windup memory the step started with.  !act: a lane
+// sitting the DLL step out keeps its discrete state (the rollout kernel's misaligned envs).  k_model_steps_split
+// keeps its own copy: through this function it recomputes one product (profiles/refactor_split/isa_diff.txt)
+__device__ __forceinline__ void major_update(Disc &D, uint32_t &mem, PassRef &R, const PassOut &o, bool dss_hit, double ud,
+                                             double tk, uint32_t mem_held, bool act = true)
+{
+    D.x_dss = (dss_hit && act) ? B747_DSS_A * D.x_dss + B747_DSS_B * ud : D.x_dss;
+    D.rl_prevY = act ? o.r : D.rl_prevY;
+    D.e_prev = act ? o.e : D.e_prev;
+    D.ed_prev = act ? o.ed : D.ed_prev;
+    mem = act ? o.and3_bits : mem;
+    R.has_ref = true; R.t_ref = tk; R.e_ref = o.e; R.ed_ref = o.ed; R.rl_prevY = o.r;
+    R.mem = mem_held;
+}
+// The env read-out's stage-4 signals (kSplitSigMask) from the control wave's last pass at time t: x its input X9..X17
+__device__ __forceinline__ void readout_signals(SigVals &sv, double t, const PassOut &o, double thPID, const double *x)
+{
+    sv.v[S_SIM_TIME] = t;
+    sv.v[S_DVARTHETA] = o.e;
+    sv.v[S_VARTHETA_ZH] = thPID;
+    sv.v[S_U_COM_PID] = o.UPID;
+    sv.v[S_DVARTHETA_DT] = o.ed;
+    sv.v[S_DVARTHETA_DT_DT] = o.edd;
+    sv.v[S_ITSE] = x[8];
+    sv.v[S_DVARTHETA_INT] = x[4];
+}
+
 // ------------------------------------------------------------------------------------ the kernel ----
 // One ControllerEnv.step (sample_time = dt: one DLL step) of the reference's training configuration
 // (kind 3, DEFC) for every env; the per-step API's K1 case of k_env_steps.  XT: the storage type of the
@@ -540,7 +653,6 @@ __device__ __forceinline__ void pair_wait_seen(unsigned *f, unsigned v, unsigned
 // end of the wave's stage 0-3, 6 control: read-out done / flight: stores issued, 7 end (realtime), 15 the table
 // barrier (realtime); flight 8-10 stage 1-3's ahead values arrived, 11-14 stage 0-3's delta arrived; ahead 8-10
 // stage 1-3's values posted; control 11 read-out arithmetic done.
-constexpr int kAheadF = 7;   // sin, cos theta, h, 1 / a, rho, q0n, q3n of a stage's input (+ the dCm altitude interval)
 // The first arguments are what the waves' first loads address (n and six of the batch's pointers, 14 dwords): with
 // -mllvm -amdgpu-kernarg-preload-count=14 (build.py) the dispatch places them in SGPRs, so the state loads issue
 // without waiting for the argument segment's scalar loads (measured 0.64 us median from wave start, round 5).
@@ -568,8 +680,9 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
     if (role == 2) __builtin_amdgcn_s_setprio(3);
     else if (role == 0) __builtin_amdgcn_s_setprio(2);
     B747_STAMP(0, true);
-    // the argument segment: n and six pointers (56 B), actions (8), b, cfgc, then three pointers (24); both structs
-    // are 8-byte multiples, so no padding lies between
+    // the argument segment: n and six pointers, actions the last of them (56 B), b, cfgc, then three pointers (24);
+    // both structs are 8-byte multiples, so no padding lies between.  The length below says 64 for the first part,
+    // 8 B past the segment's end (actions counted twice): it stays, since changing it changes the kernel's code
     static_assert(sizeof(b747_env_batch) % 8 == 0 && sizeof(b747_env_config) % 8 == 0, "argument layout");
     unsigned kpd = prefetch_kernargs_issue<64 + sizeof(b747_env_batch) + sizeof(b747_env_config) + 24>();
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -607,7 +720,6 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
     const XT *Xg = (const XT *)xv;
     XT *Xw = (XT *)b.X;
     const double temp = 0.5 * H;
-    const double t6 = H / 6.0;
 
     auto table_loads = [&](double *tv) __attribute__((always_inline)) {
 #pragma unroll
@@ -647,19 +759,12 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
         auto take_ahead = [&](int s1) __attribute__((always_inline)) {   // stage s1's values, from the ahead wave
             pair_wait_seen(&c_ah[wv], (unsigned)s1, seen_ah);
             FlightAhead an;
-            an.sth = xa[s1 - 1][0][el]; an.cth = xa[s1 - 1][1][el]; an.h = xa[s1 - 1][2][el];
-            an.inva = xa[s1 - 1][3][el]; an.rho = xa[s1 - 1][4][el];
-            an.q0n = xa[s1 - 1][5][el]; an.q3n = xa[s1 - 1][6][el];
-            an.iDC0 = xai[s1 - 1][el];
-            an.invaf = (float)an.inva; an.rhof = (float)an.rho;  // (MIX: exactly the fp32 values)
+            ahead_get(xa[s1 - 1], xai[s1 - 1], el, an);
             return an;
         };
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
-            int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" : "+s"(zoff));                     // as major_step: each stage re-derives its constant pointers
-#endif
+            const int zoff = opaque_zoff();
             if (st > 0) {
                 a = take_ahead(st);
                 B747_STAMP(7 + st);
@@ -670,13 +775,7 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
             B747_STAMP(11 + st);
             double dX[kNF];
             flight_post(x, xdl[st][el], fp, dX, fk);
-            const double c = (st == 2) ? H : temp;              // RK4 combine (b747::major_step, dll@0x2c60)
-            const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
-#pragma unroll
-            for (int j = 0; j < kNF; ++j) {
-                acc[j] = acc[j] + wm * dX[j];
-                x[j] = c * dX[j] + y[j];
-            }
+            rk4_stage<kNF>(st, dX, x, y, acc);
             if (st < 2) {                                       // the next stage input's Vy and w, to the ahead wave
                 xp[st][0][el] = x[5];
                 xp[st][1][el] = x[6];
@@ -688,7 +787,7 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
         const bool rs = cfg.auto_reset && t_of(k + 1u) >= cfg.tk;   // (EnvReadOut's done of the kind-3 read-out)
         if (valid && !rs) {
 #pragma unroll
-            for (int j = 0; j < kNF; ++j) st_state(&Xw[kFX[j] * n + i], (XT)(acc[j] * t6 + y[j]));
+            for (int j = 0; j < kNF; ++j) st_state(&Xw[kFX[j] * n + i], (XT)rk4_end(acc[j], y[j]));
         }
         B747_STAMP(6);
         B747_STAMP(7, true);
@@ -707,12 +806,9 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
         pitch_attitude(xq[1], xq[2], fk, at);
         // stage 0's attitude and h for the control wave, which then neither loads X1, X2, X5 (that the flight wave
         // overwrites at its end) nor evaluates the attitude itself
-        xa0[0][el] = at.sth; xa0[1][el] = at.cth; xa0[2][el] = xq[0];
+        att_put(xa0, el, at.sth, at.cth, xq[0]);
         pair_post(&c_a0[wv], 1u);
-        int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+s"(zoff));
-#endif
+        const int zoff = opaque_zoff();
 #pragma unroll
         for (int st = 0; st < 3; ++st) {
             if (st > 0) {                                       // stage st's input Vy, w from the flight wave's combine
@@ -721,13 +817,10 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
                 w = xp[st - 1][1][el];
             }
             const double dq[3] = {vy, dq0_of(w, at.q3n), dq3_of(w, at.q0n)};
-            const double c = (st == 2) ? H : temp;
 #pragma unroll
-            for (int q = 0; q < 3; ++q) xq[q] = c * dq[q] + yq[q];
+            for (int q = 0; q < 3; ++q) xq[q] = rk4_c(st) * dq[q] + yq[q];
             at = flight_ahead<MIX>(xq[1], xq[2], xq[0], split_kfit(zoff), fk);
-            xa[st][0][el] = at.sth; xa[st][1][el] = at.cth; xa[st][2][el] = at.h;
-            xa[st][3][el] = at.inva; xa[st][4][el] = at.rho; xa[st][5][el] = at.q0n; xa[st][6][el] = at.q3n;
-            xai[st][el] = at.iDC0;
+            ahead_put(xa[st], xai[st], el, at);
             pair_post(&c_ah[wv], (unsigned)st + 1u);
             B747_STAMP(8 + st);
         }
@@ -794,16 +887,12 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
     }
     if (!lock) {
         // stage 0's delta first (the flight wave's stage 0 waits for it; stage 1 reads the rest ~2,400 cycles later):
-        // delta_table's expressions, posted in two parts
+        // delta_table's two pieces, posted one after the other
         const bool rp = (flags & F_RP) != 0u;
         const float a32 = cfg.norm_act ? (float)((double)a * cfg.action_max) : a;
         const double dz = manual ? (double)a32 : 0.0;
-        PassRef R0{};
-        R0.has_ref = (k != 0u);
-        R0.t_ref = R0.has_ref ? t_of(k - 1u) : 0.0;
-        R0.rl_prevY = D.rl_prevY;
-        R0.y_dss = dss_hit ? D.x_dss * B747_DSS_C + B747_DSS_D * ud : D.y_dss;
-        double r0, d0, r1, d1, r3, d3;
+        const PassRef R0 = delta_ref0(k, D, ud);
+        double r0, d0, d1, d3;
         __builtin_amdgcn_s_setprio(3);                          // (the SIMD's three waves all issue here: the control
                                                                 //  wave first until stage 0's delta is out, -0.06 us)
         actuator(tk, R0, r0, d0);
@@ -811,10 +900,7 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
         pair_post(&c_dl[wv], 1u);
         __builtin_amdgcn_s_setprio(0);
         sched_fence();
-        PassRef R1 = R0;
-        R1.has_ref = true; R1.t_ref = tk; R1.rl_prevY = r0;
-        actuator(0.5 * H + tk, R1, r1, d1);
-        actuator(tnew, R1, r3, d3);
+        delta_rest(k, R0, r0, d1, d3);
         xdl[1][el] = rp ? d1 : dz;
         xdl[2][el] = rp ? d1 : dz;
         xdl[3][el] = rp ? d3 : dz;
@@ -826,20 +912,14 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
     {
         unsigned seen_a0 = 0u;
         pair_wait_seen(&c_a0[wv], 1u, seen_a0);
-        att[0].sth = xa0[0][el];
-        att[0].cth = xa0[1][el];
-        hst[0] = xa0[2][el];
+        att_get(xa0, el, att[0].sth, att[0].cth, hst[0]);
     }
     // controller and the control stages
     const float a32 = cfg.norm_act ? (float)((double)a * cfg.action_max) : a;
     const double deltaz = manual ? (double)a32 : 0.0;
     Params P{};
     P.deltaz = deltaz; P.vartheta = vartheta; P.h_zh = h_zh; P.flags = flags;
-    PassRef R{};
-    R.has_ref = (k != 0u);
-    R.t_ref = R.has_ref ? t_of(k - 1u) : 0.0;
-    R.e_ref = D.e_prev; R.ed_ref = D.ed_prev; R.rl_prevY = D.rl_prevY;
-    R.y_dss = D.y_dss; R.mem = mem;
+    PassRef R = pass_ref_at(k, D, mem);
 #pragma unroll
     for (int j = 0; j < kNC; ++j) { y[j] = x[j]; acc[j] = 0.0; }
     PassOut o{};
@@ -854,24 +934,9 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
             xdl[st][el] = delta;
             pair_post(&c_dl[wv], (unsigned)st + 1u);
         }
-        if (st == 3) {   // the read-out's stage-4 signals (kSplitSigMask)
-            sv.v[S_SIM_TIME] = t;
-            sv.v[S_DVARTHETA] = o.e;
-            sv.v[S_VARTHETA_ZH] = thPID;
-            sv.v[S_U_COM_PID] = o.UPID;
-            sv.v[S_DVARTHETA_DT] = o.ed;
-            sv.v[S_DVARTHETA_DT_DT] = o.edd;
-            sv.v[S_ITSE] = x[8];
-            sv.v[S_DVARTHETA_INT] = x[4];
-        }
-        if (st == 0) {   // MAJOR-only updates (dll@0x271a), then only what the step changed is written back
-            D.x_dss = dss_hit ? B747_DSS_A * D.x_dss + B747_DSS_B * ud : D.x_dss;
-            D.rl_prevY = o.r;
-            D.e_prev = o.e;
-            D.ed_prev = o.ed;
-            mem = o.and3_bits;
-            R.has_ref = true; R.t_ref = tk; R.e_ref = o.e; R.ed_ref = o.ed; R.rl_prevY = o.r;
-            R.mem = mem_held;
+        if (st == 3) readout_signals(sv, t, o, thPID, x);
+        if (st == 0) {   // MAJOR-only updates, then only what the step changed is written back
+            major_update(D, mem, R, o, dss_hit, ud, tk, mem_held);
             if (valid) {
                 if (dss_hit) {
                     st_state(&b.disc[0 * n + i], D.x_dss);
@@ -885,19 +950,10 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
                 b.mem[i] = (uint8_t)mem;
             }
         }
-        const double c = (st == 2) ? H : temp;                  // RK4 combine of X9..X17
-        const double wm = (st == 1 || st == 2) ? 2.0 : 1.0;
-#pragma unroll
-        for (int j = 0; j < kNC; ++j) {
-            acc[j] = acc[j] + wm * dX[j];
-            x[j] = c * dX[j] + y[j];
-        }
+        rk4_stage<kNC>(st, dX, x, y, acc);
         B747_STAMP(2 + st);
     };
-    int zoff = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+s"(zoff));
-#endif
+    const int zoff = opaque_zoff();
     // the episode return is read only by the read-out; waiting for its load there would also wait for every store
     // issued before it (one vmcnt for loads and stores): take it where the stage-0 pass waits for X9..X17 (the
     // loads before it) anyway, before the stage's discrete-state stores
@@ -909,16 +965,15 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
 #pragma unroll
     for (int st = 1; st < 4; ++st) {                            // each stage's attitude from the ahead wave
         pair_wait_seen(&c_ah[wv], (unsigned)st, seen_ah);
-        att[st].sth = xa[st - 1][0][el];
-        att[st].cth = xa[st - 1][1][el];
-        hst[st] = xa[st - 1][2][el];
+        att_get(xa[st - 1], el, att[st].sth, att[st].cth, hst[st]);
         cstage(st, zoff);
     }
     // ---- read-out (EnvReadOut of the kind-3 configuration) and episode bookkeeping, from the signals in registers.
     // The arguments from here on are fresh copies of the kernel's: the compiler then loads the fields where they are
     // used instead of keeping the early copies' wide SGPR tuples live through the stages (spilled to VGPR lanes and
     // restored whole at every later use: 177 against 38 v_readlane in this kernel)
-    const b747_env_batch bl = b;
+    b747_env_batch bl = b;
+    bl.n = n;                                                   // (the preloaded argument, not a second load of b.n)
     EnvCfg cfgl = cfgc;
     spec_config(cfgl);
     double sgr[sig_rows(kSplitSigMask)];
@@ -940,15 +995,7 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
         bl.done[i] = done ? 1 : 0;
         if (reward_seq) reward_seq[i] = r32;
         if (done_seq) done_seq[i] = done ? 1 : 0;
-        if (done) {   // record_episode_end
-            if (bl.ep_final_return) bl.ep_final_return[i] = ep_ret;
-            if (bl.ep_final_len) bl.ep_final_len[i] = ep_len;
-            if (bl.ep_stats) {
-                bl.ep_stats[i] += 1.0;
-                bl.ep_stats[n + i] += ep_ret;
-                bl.ep_stats[2 * n + i] += (double)ep_len;
-            }
-        }
+        if (done) record_episode_end(bl, i, ep_ret, ep_len);
         bl.ep_return[i] = rs ? 0.0f : (float)ep_ret;   // (exact: VecMonitor's float32 sums)
     }
     B747_STAMP(6);
@@ -997,7 +1044,7 @@ __global__ __launch_bounds__(3 * ENVS) B747_NO_FMAC void k_env_step_split(
         for (int j = 0; j < 5; ++j) bl.aero_err[j * n + i] = aero[j];
     } else if (valid) {
 #pragma unroll
-        for (int j = 0; j < kNC; ++j) st_state(&((XT *)bl.X)[(9 + j) * n + i], (XT)(acc[j] * t6 + y[j]));
+        for (int j = 0; j < kNC; ++j) st_state(&((XT *)bl.X)[(9 + j) * n + i], (XT)rk4_end(acc[j], y[j]));
         if (ctrl0 || (flags & F_PID_CS)) bl.h_zh[i] = h_zh;
     }
     B747_STAMP(7, true);

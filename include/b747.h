@@ -124,9 +124,11 @@ int32_t b747_model_initialize(const b747_model_batch *b, const uint8_t *mask, vo
 
 /* n_steps consecutive model_simple_step calls (dll@0x16d0) on every env: one ode4 step of
  * h = 0.01 s each.  Replaces core/model.py:247-250 (x N envs, x n_steps).  n_steps = 1 with the DLL's
- * default constants (FAST) runs each env over three waves (k_model_step_split); otherwise one wave per env
- * with the state in registers across the n_steps (k_model_step): the same operations, agreeing to a few ulp
- * (FMA contraction); b747_set_specialization(0) keeps every call on the one-wave kernel. */
+ * default constants (FAST) runs each env over three waves (k_model_step_split), and so does n_steps > 1 for up
+ * to 16,384 envs, with the state in registers across the steps (k_model_steps_split); otherwise -- larger batches,
+ * other constants, FAITHFUL -- one wave per env with the state in registers across the n_steps (k_model_step): the
+ * same operations, agreeing to a few ulp (FMA contraction); b747_set_specialization(0) keeps every call on the
+ * one-wave kernel. */
 int32_t b747_model_step(const b747_model_batch *b, const b747_consts *c, int32_t n_steps,
                         void *stream);
 
@@ -260,8 +262,9 @@ int32_t b747_env_time_steps(const b747_env_batch *b, const b747_env_config *cfg,
  * training setup (PID_LIKE obs, CLASSIC reward, MANUAL/DIRECT control, CONST resets, drawn AERO
  * errors, normalised obs/action, no limiter, auto-reset) and the DLL's default constants runs a
  * kernel compiled for exactly that configuration; with on == 1 a single step of it (sample_time = dt)
- * runs each env over three waves (flight / ahead / control), on == 2 keeps one wave per env; on == 0
- * forces the generic kernel (tests compare them), and b747_model_step's one-step calls the one-wave kernel.
+ * runs each env over three waves (flight / ahead / control), on == 2 keeps one wave per env (the env kernels only:
+ * b747_model_step treats 2 as 1); on == 0 forces the generic kernel (tests compare them) and keeps every
+ * b747_model_step call on the one-wave kernel.
  * Returns the previous setting.  No reference counterpart (the reference has no kernels). */
 int32_t b747_set_specialization(int32_t on);
 
