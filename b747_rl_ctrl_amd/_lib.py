@@ -7,9 +7,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # B747_LIB_PATH: an A/B build to load instead of the product library (tools/ab_*.sh); the product .so is never
 # overwritten by a variant, so an interrupted A/B run cannot leave one in its place
 LIB_PATH = os.environ.get("B747_LIB_PATH") or os.path.join(HERE, "libb747.so")
-ABI_VERSION = 10         # include/b747.h B747_ABI_VERSION
+ABI_VERSION = 11         # include/b747.h B747_ABI_VERSION
 
 NX, NDISC, NSIG, NAERO = 18, 9, 31, 5
+EVAL_ROWS = ("overshoot", "rise_time", "settling_time", "static_error", "itse", "length", "return")   # B747_NEVAL
 F_PID_SS, F_PID_CS, F_RP, F_RL = 1, 2, 4, 8
 VARIANT_FAST, VARIANT_FAITHFUL, VARIANT_MIXED = 0, 1, 2
 
@@ -58,6 +59,7 @@ _lib = None
 
 _V, _I32, _I64, _U32, _U64, _F32 = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32,
                                     ctypes.c_uint64, ctypes.c_float)
+_F64 = ctypes.c_double
 _PM, _PE, _PC, _PK = (ctypes.POINTER(ModelBatch), ctypes.POINTER(EnvBatch), ctypes.POINTER(EnvConfig),
                       ctypes.POINTER(Consts))
 
@@ -83,6 +85,7 @@ SIGNATURES = {
     "b747_policy_pack": ([_V, _I32, _V], _I32),
     "b747_policy_act": ([_V, _I32, _I64, _V, _V, _U64, _V, _U32, _I64, _V, _V, _V, _V, _V, _F32, _F32, _V], _I32),
     "b747_ppo_rollout": ([_PE, _PC, _PK, _V, _U64, _V, _I32] + [_V] * 6 + [_F32, _F32, _V], _I32),
+    "b747_eval_episodes": ([_PE, _PC, _PK, _V, _I32, _I32, _F64, _V, _F64, _F32, _F32, _V, _V], _I32),
 }
 
 

@@ -8,7 +8,10 @@ ROOT = os.path.dirname(HERE)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("B747_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = [os.path.join(HERE, "csrc", "b747_kernels.hip"), os.path.join(HERE, "csrc", "b747_fast.hip")]
+# (the evaluation-episode kernels, csrc/b747_eval.h, are translation units of their own, FAITHFUL / FAST as the first
+# two: compiled inside those, they changed the generated code of kernels already there)
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("b747_kernels.hip", "b747_fast.hip", "b747_eval_faithful.hip",
+                                                   "b747_eval_fast.hip")]
 DEPS = SOURCES + sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))
                         if f.endswith(".h")) + [os.path.join(ROOT, "include", "b747.h"),
                                                 os.path.join(ROOT, "include", "b747_tables.h"),

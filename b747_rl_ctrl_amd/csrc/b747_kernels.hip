@@ -21,6 +21,7 @@
 #include "b747_env.h"
 #include "b747_lanes.h"
 #include "b747_policy.h"
+#include "b747_eval_args.h"
 
 using namespace b747;
 
@@ -181,6 +182,37 @@ __attribute__((visibility("default"))) int32_t b747_ppo_rollout(const b747_env_b
                        params, rows, obs_buf, val_buf, step_base, (uint32_t)T);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail(e, "b747_ppo_rollout");
+}
+
+__attribute__((visibility("default"))) int32_t b747_eval_episodes(const b747_env_batch *b, const b747_env_config *cfg,
+                                                                   const b747_consts *c, const float *params,
+                                                                   int32_t n_env_steps, int32_t sig_row, double scale,
+                                                                   const double *y_base, double error_band,
+                                                                   float act_lo, float act_hi, double *eval_out,
+                                                                   void *stream)
+{
+    int32_t r = check_env(b, cfg);
+    if (r <= 0) return r;
+    if (!c) return bad_arg("consts is NULL");
+    if (!y_base || !eval_out) return bad_arg("y_base / eval_out is NULL");
+    if (n_env_steps < 0) return bad_arg("n_env_steps < 0");
+    if (sig_row < 0 || sig_row >= B747_NSIG) return bad_arg("sig_row (a B747_SIG_* row)");
+    if (!(act_lo <= act_hi)) return bad_arg("act_lo > act_hi");
+    if (!b->x_f64) return bad_arg("b747_eval_episodes: x_f64 (the episode kernel keeps fp64 state only)");
+    if (cfg->auto_reset != 0)
+        return bad_arg("b747_eval_episodes: auto_reset must be 0 (an episode ends at its first done)");
+    if (params && b->obs_dim != 3 && b->obs_dim != 5)
+        return bad_arg("b747_eval_episodes: obs_dim (a policy runs with PID_LIKE 3 or SPEED_MODE 5 only; "
+                       "other observation types take params = NULL)");
+    if (!params && !b->action) return bad_arg("b747_eval_episodes: action is NULL (params = NULL holds b->action)");
+    if (n_env_steps == 0) return 0;
+    const EvalArgs ea{params, n_env_steps, sig_row, scale, y_base, error_band, act_lo, act_hi, eval_out};
+    const Consts C = consts_of(c);   // run-time constants: no instantiation of this kernel needs the DLL's defaults
+    const int od = params ? b->obs_dim : 0;
+    if (b->variant != B747_VARIANT_FAITHFUL) launch_eval_episodes_fast(*b, *cfg, C, ea, od, (hipStream_t)stream);
+    else launch_eval_episodes_faithful(*b, *cfg, C, ea, od, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(e, "b747_eval_episodes");
 }
 
 __attribute__((visibility("default"))) int32_t b747_consts_default(b747_consts *c)

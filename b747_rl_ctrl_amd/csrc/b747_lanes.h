@@ -390,17 +390,26 @@ __device__ __forceinline__ void env_reset_lane(const b747_env_batch &b, const En
     L.s.ep_len = 0;
 }
 
+// Per-DLL-step hook of env_step_lane: the default does nothing and asks for no read-out.  A hook with kEveryStep
+// gets the signal stash of every DLL step of the env step (as the recording kind does), right after that step
+// (k_eval_episodes, b747_eval.h).  Passed as a pointer, NULL by default: a reference to a default-constructed hook
+// changed the register numbering of every k_env_steps instantiation.
+struct NoDllStepHook {
+    static constexpr bool kEveryStep = false;
+    __device__ __forceinline__ void operator()(const double *, int) const {}
+};
+
 // One ControllerEnv.step for this lane; returns done.  ONE: the caller guarantees n_sub == 1 (sample_time
 // = dt), so the sub-step loop is a single straight-line DLL step.
 // EARLY (with ONE, per-step kernel only): the discrete state / k / mem are stored right after the MAJOR
 // pass and X right after the RK4 combine, before the read-out -- their stores drain while the wave still
 // computes instead of in one burst at the end of every wave (env_store<..., EARLY> skips them).
 template <bool FAST, bool REC, uint32_t SIGMASK = kAllSignals, bool ONE = false, bool EARLY = false,
-          typename XT = double>
+          typename XT = double, class DLLHOOK = NoDllStepHook>
 __device__ __forceinline__ bool env_step_lane(const b747_env_batch &b, const EnvCfg &cfg, const Consts &C,
                                               int64_t i, EnvLane &L, float a, float *obs_row, float *obs_row2,
                                               float *term_row, float &reward_out, const double *tb, double *sg,
-                                              int sst, int step_ix = 0)
+                                              int sst, int step_ix = 0, const DLLHOOK *dll_hook = nullptr)
 {
     static_assert(!EARLY || ONE, "early state stores need the single-DLL-step path");
     // env/ctrl_env.py:262-264: action *= action_max, in place on a float32 array
@@ -466,12 +475,13 @@ __device__ __forceinline__ bool env_step_lane(const b747_env_batch &b, const Env
         }
     };
     for (uint32_t q = 0; q < steps; ++q) {
-        major_step<FAST>(L.x, L.D, L.k, L.mem, C, P, tb, stash, rec || q + 1u == steps, early_disc);
+        major_step<FAST>(L.x, L.D, L.k, L.mem, C, P, tb, stash, rec || DLLHOOK::kEveryStep || q + 1u == steps, early_disc);
         if (rec) {
             double *row = b.sig + (int64_t)(nsub - steps + q) * NSIG * b.n;
 #pragma unroll
             for (int j = 0; j < NSIG; ++j) row[j * b.n + i] = sg[j * sst];
         }
+        if (DLLHOOK::kEveryStep) (*dll_hook)(sg, sst);
     }
     if (rec && b.rec_params) {   // the parameters this env step ran with (Storage columns vartheta_ref, hzh)
         b.rec_params[i] = L.vartheta;

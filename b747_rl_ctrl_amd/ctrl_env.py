@@ -365,6 +365,45 @@ class BatchControllerEnv:
                                             ptr(done_seq), s.cuda_stream), "b747_env_rollout")
         return self.obs, self.reward, self.done
 
+    def eval_episodes(self, n_env_steps: int, params: Optional[torch.Tensor] = None, signal: str = "state_vartheta",
+                      scale: float = 1.0, y_base=None, error_band: float = 0.05, action=None, act_lo: float = None,
+                      act_hi: float = None, stream=None):
+        """One whole episode per env in ONE launch (b747_eval_episodes, include/b747.h): up to n_env_steps env
+        steps from the current state, each env ending at its first done (the env needs auto_reset=False), with
+        the reference's calc_stepinfo of `scale * nan_to_num(signal)` against y_base [N] accumulated inside the
+        kernel -- no history is recorded.  params: the packed policy buffer (PPO.flat, or ActorCritic parameters
+        through b747_policy_pack; PID_LIKE / SPEED_MODE observations); the action is its mean clipped to [act_lo,
+        act_hi] (default: the action space).  params None: `action` [N] (default 0) is held for the whole episode
+        -- ignored where the SS PID flies (AUTO / FULL_AUTO).  y_base defaults to scale * the constant pitch
+        reference.  Returns {"overshoot" (signed %), "rise_time", "settling_time", "static_error", "itse",
+        "length" (DLL steps), "return"}: [N] float64 tensors."""
+        from .model import SIG
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        b = self._batch()
+        with torch.cuda.stream(s):
+            yb = self.ref[0] * scale if y_base is None else \
+                torch.as_tensor(y_base, dtype=torch.float64, device=self.device).expand(self.n)
+            yb = yb.to(torch.float64).contiguous()
+            out = torch.empty(len(_lib.EVAL_ROWS), self.n, dtype=torch.float64, device=self.device)
+            if params is None:
+                if action is None:
+                    self.action.zero_()
+                else:
+                    self.action.copy_(torch.as_tensor(action, dtype=torch.float32).to(self.device).expand(self.n))
+                b.action = self.action.data_ptr()
+            else:
+                assert params.dtype == torch.float32 and params.is_contiguous() and params.device == self.device \
+                    and params.numel() >= int(self._L.b747_policy_num_params(self.obs_dim)), \
+                    "params: the packed fp32 policy buffer (b747_policy_num_params floats) on the env's device"
+        lo = float(self.action_space.low) if act_lo is None else float(act_lo)
+        hi = float(self.action_space.high) if act_hi is None else float(act_hi)
+        _lib.check(self._L.b747_eval_episodes(self._bref, self._cref, self._kref,
+                                              None if params is None else ctypes.c_void_p(params.data_ptr()),
+                                              int(n_env_steps), SIG[signal], float(scale), ctypes.c_void_p(yb.data_ptr()),
+                                              float(error_band), lo, hi, ctypes.c_void_p(out.data_ptr()), s.cuda_stream),
+                   "b747_eval_episodes")
+        return {k: out[j] for j, k in enumerate(_lib.EVAL_ROWS)}
+
     def step_seq(self, actions: torch.Tensor, stream=None):
         """len(actions) consecutive step() calls with actions [T, N] known in advance: T launches of the
         per-step kernel issued by one C call (b747_env_step_seq), so a host loop's per-call Python cost is

@@ -14,6 +14,9 @@ Semantics kept from calc_stepinfo(ys, y_base, error_band=0.05, ts):
   rise_time      ts[first i < T-1 with (ys[i]-ys[0])/(y_base-ys[0]) >= 1-band] - ts[0]; NaN if none
   settling_time  ts[last i outside the [1-band, 1+band] ratio band] - ts[0]; NaN if none
   static_error   |ys[-1] - y_base|
+run_step_tests drives the env from Python, one recording launch per env step; run_step_tests_fused,
+monte_carlo_step_tests and PPO.step_tests fly the same episodes inside ONE kernel launch with the policy in the loop and
+the metrics accumulated in registers (b747_eval_episodes, include/b747.h).
 (None in the reference -> NaN here; the reference raises ZeroDivisionError when y_base == ys[0],
 which gives NaN/inf ratios here.)
 """
@@ -110,4 +113,107 @@ def run_step_tests(policy: Callable[[torch.Tensor], torch.Tensor], vartheta_ref:
     out["mean_settling_time"] = out["settling_time"].mean()
     out["mean_overshoot"] = out["overshoot"].mean()
     out["mean_quality"] = q.mean()
+    return out
+
+
+# ------------------------------------------------------------------ whole episodes in one launch --
+
+def packed_policy(policy, obs_dim: int, device) -> Optional[torch.Tensor]:
+    """The packed fp32 buffer b747_eval_episodes reads (include/b747.h b747_policy_pack) for an ActorCritic, a
+    fused PPO (its own `flat`, packed by sync_params) or None (no policy)."""
+    if policy is None:
+        return None
+    flat = getattr(policy, "flat", None)
+    if flat is not None:                          # PPO(fused=True)
+        return flat
+    if hasattr(policy, "policy") and hasattr(policy.policy, "flat_params"):   # PPO(fused=False)
+        policy = policy.policy
+    from . import _lib
+    L = _lib.lib()
+    n = int(L.b747_policy_num_params(obs_dim))
+    _lib.check(min(n, 0), "b747_policy_num_params")
+    buf = torch.zeros(n, dtype=torch.float32, device=device)
+    with torch.no_grad():
+        fp = policy.flat_params().to(device=device, dtype=torch.float32)
+        buf[:fp.numel()].copy_(fp)
+    _lib.check(L.b747_policy_pack(buf.data_ptr(), obs_dim, torch.cuda.current_stream(buf.device).cuda_stream),
+               "b747_policy_pack")
+    return buf
+
+
+def _fused_out(env: BatchControllerEnv, ev: Dict[str, torch.Tensor], vref: torch.Tensor, tk: float):
+    q = quality(ev["itse"], vref, tk)
+    out = {"settling_time": ev["settling_time"], "overshoot": ev["overshoot"].abs(), "rise_time": ev["rise_time"],
+           "static_error": ev["static_error"], "quality": q, "done": env.done.clone(),
+           "length": ev["length"].to(torch.int64), "return": ev["return"]}
+    out["mean_settling_time"] = out["settling_time"].mean()
+    out["mean_overshoot"] = out["overshoot"].mean()
+    out["mean_quality"] = q.mean()
+    return out
+
+
+def run_step_tests_fused(policy, vartheta_ref: Sequence[float],
+                         state0: Sequence[float] = (0, 11000, 250, 0, 0, 0), tk: float = 60.0,
+                         observation_type: ObservationType = ObservationType.PID_LIKE,
+                         reward_type: RewardType = RewardType.CLASSIC,
+                         ctrl_mode: Optional[CtrlMode] = CtrlMode.DIRECT_CONTROL, norm_obs: bool = True,
+                         norm_act: bool = True, sample_time: Optional[float] = None, replicas: int = 1, device="cuda",
+                         ctrl_type: CtrlType = CtrlType.MANUAL, action=None, **env_kwargs) -> Dict[str, torch.Tensor]:
+    """run_step_tests with every episode flown inside ONE kernel launch (BatchControllerEnv.eval_episodes): the
+    deterministic policy runs in the kernel's step loop and the step-response metrics accumulate in registers, so
+    neither the per-step host round trips nor the [steps, n_sub, N] history of run_step_tests exist.
+
+    policy: an ActorCritic, a PPO (its packed `flat` buffer) or None -- then `action` [N] or scalar (default 0) is
+    held for the whole episode; with ctrl_type AUTO / FULL_AUTO the SS PID flies and the action is ignored (the
+    PID baseline of agent_test.pid_baseline_env).  Same series (theta * (180 / pi) against vref * 180 / pi) and the
+    same keys as run_step_tests, plus "return" (the episode return)."""
+    refs = torch.tensor(list(vartheta_ref) * replicas, dtype=torch.float64, device=device)
+    n = refs.numel()
+    env = BatchControllerEnv(n, observation_type, reward_type, norm_obs, norm_act, ctrl_type, ctrl_mode,
+                             reset_ref_mode=None, tk=tk, sample_time=sample_time, auto_reset=False,
+                             device=device, **env_kwargs)
+    env.set_state0(torch.tensor(state0, dtype=torch.float64))
+    env.set_reference(vartheta=refs)
+    env.reset()
+    steps = int(math.ceil(tk / env.sample_time - 1e-9))
+    vref = env.ref[0].to(torch.float64)
+    ev = env.eval_episodes(steps, packed_policy(policy, env.obs_dim, env.device), "state_vartheta",
+                           scale=180 / math.pi, y_base=vref * 180 / math.pi, action=action)
+    out = _fused_out(env, ev, vref, tk)
+    out["env"] = env
+    return out
+
+
+def monte_carlo_step_tests(policy, n: int, seed: int = 0, tk: float = 20.0,
+                           observation_type: ObservationType = ObservationType.PID_LIKE,
+                           reward_type: RewardType = RewardType.CLASSIC,
+                           ctrl_mode: Optional[CtrlMode] = CtrlMode.DIRECT_CONTROL, norm_obs: bool = True,
+                           norm_act: bool = True, sample_time: Optional[float] = 0.05, env_offset: int = 0,
+                           quantiles: Sequence[float] = (0.05, 0.5, 0.95), device="cuda",
+                           **env_kwargs) -> Dict[str, torch.Tensor]:
+    """A Monte-Carlo robustness test of one controller: n envs with the reference's random resets (CONST pitch
+    references, random initial states, drawn aerodynamic errors: core/controller.py:134-201), one step-response
+    episode each, all in one launch.  The draws are Philox streams keyed by (seed, env_offset + i), so env i's
+    result does not depend on how the n envs are split into batches (shard with env_offset).
+
+    Returns the per-env metrics of run_step_tests_fused plus "vartheta_ref" [n], and for each metric m:
+    "<m>_quantiles" [len(quantiles)] over the envs where it is defined and "<m>_nan_share" (rise / settling time
+    are NaN for an env that never rises / never leaves the band)."""
+    from .ctrl_env import DisturbanceMode, ResetRefMode
+    env = BatchControllerEnv(n, observation_type, reward_type, norm_obs, norm_act, CtrlType.MANUAL, ctrl_mode,
+                             reset_ref_mode=ResetRefMode.CONST, disturbance_mode=DisturbanceMode.AERO_DISTURBANCE,
+                             tk=tk, sample_time=sample_time, auto_reset=False, seed=seed, env_offset=env_offset,
+                             device=device, **env_kwargs)      # (the constructor resets once: the draws)
+    steps = int(math.ceil(tk / env.sample_time - 1e-9))
+    vref = env.ref[0].to(torch.float64).clone()
+    ev = env.eval_episodes(steps, packed_policy(policy, env.obs_dim, env.device), "state_vartheta",
+                           scale=180 / math.pi, y_base=vref * 180 / math.pi)
+    out = _fused_out(env, ev, vref, tk)
+    out["vartheta_ref"] = vref
+    qs = torch.tensor(list(quantiles), dtype=torch.float64, device=env.device)
+    for m in ("overshoot", "rise_time", "settling_time", "static_error", "quality"):
+        v = out[m]
+        nan = torch.isnan(v)
+        out[m + "_nan_share"] = nan.double().mean()
+        out[m + "_quantiles"] = torch.nanquantile(v, qs) if not bool(nan.all()) else torch.full_like(qs, math.nan)
     return out

@@ -432,3 +432,21 @@ class PPO:
             self.compute_gae(T)
             hist.append(self.train(T) | {"mean_reward": float(self.rew_buf[:T].mean())})
         return hist
+
+    def step_tests(self, vartheta_ref, state0=(0, 11000, 250, 0, 0, 0), tk: Optional[float] = None, **kwargs):
+        """The reference's ControlTestCallback.calc_stepinfo (neural/callbacks.py:60-100) for the current policy:
+        one closed-loop step-response episode per pitch reference on a fresh test env with this env's observation
+        / reward / control settings, all inside ONE kernel launch (evaluate.run_step_tests_fused), so a training
+        loop can call it between rollouts without leaving the device.  Returns run_step_tests' metrics."""
+        from .evaluate import run_step_tests_fused
+        e = self.env
+        if self.fused:
+            policy = self                     # the packed buffer the rollout kernels read (self.flat)
+        else:
+            policy = self.policy
+        kw = dict(observation_type=e.observation_type, reward_type=e.reward_type, ctrl_mode=e.ctrl_mode,
+                  norm_obs=e.norm_obs, norm_act=e.norm_act, sample_time=e.sample_time, device=e.device,
+                  action_max=e.action_max, vartheta_max=e.vartheta_max, use_limiter=e.use_limiter,
+                  variant={0: "fast", 1: "faithful", 2: "mixed"}[e.variant])
+        kw.update(kwargs)
+        return run_step_tests_fused(policy, vartheta_ref, state0=state0, tk=e.tk if tk is None else tk, **kw)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define B747_ABI_VERSION 10  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
+#define B747_ABI_VERSION 11  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
                                 * 3: + b747_env_batch.rec_params, b747_struct_size; 4: + b747_env_batch.ep_stats;
                                 * 5: + b747_env_step_seq; 6: b747_model_batch.aero_err is double (the DLL's
                                 * `double aero_err[5]`, core/model.py:164), the policy buffer gains the layer-1
@@ -35,7 +35,7 @@ extern "C" {
                                 * the two-wave kernels run sample_time > dt (n_sub DLL steps per env step); 9: + b747_env_kernel,
                                 * and ep_return / ep_final_return accumulate as SB3's VecMonitor (float32); 10:
                                 * b747_ppo_rollout advances *step_base by T on the device, b747_env_batch.ep_return is float
-                                * (it holds float32 values; 8 B less per env step) */
+                                * (it holds float32 values; 8 B less per env step); 11: + b747_eval_episodes */
 
 #define B747_NX 18   /* continuous states, SURVEY A.1 (dll.data@0x2b380) */
 #define B747_NDISC 9 /* compact discrete state, see b747_model_batch.disc */
@@ -318,6 +318,30 @@ int32_t b747_policy_act(const float *params, int32_t obs_dim, int64_t n, const f
                         float *obs_out, float *act_out,
                         float *logp_out, float *value_out, float *env_action, float act_lo, float act_hi,
                         void *stream);
+
+/* ---- whole evaluation episodes in one launch (ControlTestCallback.calc_stepinfo, neural/callbacks.py:60-100) ----
+ * Every env flies one episode from its current state: up to n_env_steps env steps, ending at its first done
+ * (t >= tk, or the limiter); from then on the env is frozen -- its stored state is the state at that done -- while
+ * the launch goes on for the others.  The action of a step is the policy's mean (params: the buffer b747_policy_pack
+ * filled; the policy head only, no noise) on the env's observation, clipped to [act_lo, act_hi] (step 0 reads
+ * b->obs); with params == NULL it is b->action[i], held for the whole episode (ignored where the SS PID flies:
+ * the PID baseline; an open-loop elevator step otherwise).  After every DLL step (n_sub per env step) the sample
+ * scale * nan_to_num(signal sig_row) at sim_time goes into a per-env running calc_stepinfo (tools/general.py:46-61)
+ * against y_base[i] with the given error band; no history is kept.  eval_out [B747_NEVAL][N] (double): overshoot (%,
+ * signed; NaN if y_base == 0), rise_time, settling_time (s; NaN if none), static_error, the ITSE signal at the end,
+ * the episode's length in DLL steps, and the episode return (VecMonitor's float32 accumulation, from b->ep_return).
+ * obs / reward / done, ep_return and the ep_final_* / ep_stats buffers are left as a step loop would leave them at the
+ * env's last step.  One wave per 64 envs on the generic lane code (every configuration b747_env_step covers, run-time
+ * constants, FAST or FAITHFUL arithmetic; MIXED runs FAST).  Returns -hipErrorInvalidValue for fp32 state
+ * (x_f64 == 0), cfg->auto_reset != 0, or a policy with an obs_dim other than 3 / 5.  n_env_steps == 0 validates and
+ * launches nothing.  Stream-ordered, graph-capturable, no allocation. */
+#define B747_NEVAL 7  /* rows of eval_out: overshoot, rise_time, settling_time, static_error,
+                         ITSE at the end, length in DLL steps, episode return */
+int32_t b747_eval_episodes(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c,
+                           const float *params /* packed by b747_policy_pack; NULL = no policy */,
+                           int32_t n_env_steps, int32_t sig_row, double scale, const double *y_base /* [N] */,
+                           double error_band, float act_lo, float act_hi,
+                           double *eval_out /* [B747_NEVAL][N] */, void *stream);
 
 /* Human-readable text of the last error returned on this thread. */
 const char *b747_last_error(void);
