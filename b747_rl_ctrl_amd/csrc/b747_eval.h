@@ -131,7 +131,15 @@ __global__ __launch_bounds__(kEvalBlock) B747_NO_FMAC void k_eval_episodes(b747_
             }
             if (done) {
                 live = false;
-                if (owner) record_episode_end(b, i, L);
+                if (owner) {
+                    record_episode_end(b, i, L);
+                    // auto_reset is 0 here, so the row of the done step is the terminal observation (EnvReadOut
+                    // writes the same values to both); b.obs_dim entries, with a policy or without
+                    if (b.terminal_obs) {
+                        const int od = OD > 0 ? OD : b.obs_dim;
+                        for (int k = 0; k < od; ++k) b.terminal_obs[i * od + k] = orow[k];
+                    }
+                }
             }
         }
     }
@@ -140,6 +148,11 @@ __global__ __launch_bounds__(kEvalBlock) B747_NO_FMAC void k_eval_episodes(b747_
     if constexpr (OD > 0) {
 #pragma unroll
         for (int k = 0; k < OD; ++k) b.obs[i * OD + k] = o[k];
+    } else {
+        // no policy: any observation type.  The lane's LDS row holds its last read-out (every lane is live in its
+        // first step, and n_env_steps >= 1 in every launch)
+        const int od = b.obs_dim;
+        for (int k = 0; k < od; ++k) b.obs[i * od + k] = sobs[lane][k];
     }
     b.reward[i] = r_last;
     b.done[i] = live ? 0 : 1;

@@ -330,11 +330,12 @@ int32_t b747_policy_act(const float *params, int32_t obs_dim, int64_t n, const f
  * against y_base[i] with the given error band; no history is kept.  eval_out [B747_NEVAL][N] (double): overshoot (%,
  * signed; NaN if y_base == 0), rise_time, settling_time (s; NaN if none), static_error, the ITSE signal at the end,
  * the episode's length in DLL steps, and the episode return (VecMonitor's float32 accumulation, from b->ep_return).
- * obs / reward / done, ep_return and the ep_final_* / ep_stats buffers are left as a step loop would leave them at the
- * env's last step.  One wave per 64 envs on the generic lane code (every configuration b747_env_step covers, run-time
- * constants, FAST or FAITHFUL arithmetic; MIXED runs FAST).  Returns -hipErrorInvalidValue for fp32 state
- * (x_f64 == 0), cfg->auto_reset != 0, or a policy with an obs_dim other than 3 / 5.  n_env_steps == 0 validates and
- * launches nothing.  Stream-ordered, graph-capturable, no allocation. */
+ * obs / reward / done, terminal_obs (where non-NULL, written at the done), ep_return and the ep_final_* / ep_stats
+ * buffers are left as a step loop would leave them at the env's last step, with a policy or without (obs_dim entries
+ * per row, any observation type).  One wave per 64 envs on the generic lane code (every configuration b747_env_step
+ * covers, run-time constants, FAST or FAITHFUL arithmetic; MIXED runs FAST).  Returns -hipErrorInvalidValue for fp32
+ * state (x_f64 == 0), cfg->auto_reset != 0, or a policy with an obs_dim other than 3 / 5.  n_env_steps == 0 validates
+ * and launches nothing.  Stream-ordered, graph-capturable, no allocation. */
 #define B747_NEVAL 7  /* rows of eval_out: overshoot, rise_time, settling_time, static_error,
                          ITSE at the end, length in DLL steps, episode return */
 int32_t b747_eval_episodes(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c,
