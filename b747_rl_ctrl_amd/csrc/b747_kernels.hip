@@ -22,6 +22,8 @@
 #include "b747_lanes.h"
 #include "b747_policy.h"
 #include "b747_eval_args.h"
+#define B747_PPO_UPDATE_NO_KERNELS   // the update kernels live in b747_ppo_update.hip; this unit calls their launchers
+#include "b747_ppo_update.h"
 
 using namespace b747;
 
@@ -86,6 +88,8 @@ int32_t check_batch(const b747_model_batch *b, bool need_params)
         return bad_arg("parameter pointer is NULL");
     return 1;
 }
+
+bool policy_obs_dim_ok(int32_t od) { return od == 3 || od == 5 || od == 7 || od == 8 || od == 10; }
 
 }  // namespace
 
@@ -213,6 +217,51 @@ __attribute__((visibility("default"))) int32_t b747_eval_episodes(const b747_env
     else launch_eval_episodes_faithful(*b, *cfg, C, ea, od, (hipStream_t)stream);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : fail(e, "b747_eval_episodes");
+}
+
+__attribute__((visibility("default"))) int64_t b747_ppo_update_workspace(int32_t obs_dim)
+{
+    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("obs_dim (3, 5, 7, 8 or 10)");
+    return upd_ws_bytes(obs_dim);
+}
+
+__attribute__((visibility("default"))) int32_t b747_ppo_grad(const float *theta, int32_t obs_dim, const float *obs,
+                                                              const float *act, const float *old_logp, const float *adv,
+                                                              const float *ret, const int64_t *idx, int64_t batch,
+                                                              double clip_range, double ent_coef, double vf_coef,
+                                                              void *workspace, float *grad, float *stats, void *stream)
+{
+    if (!theta) return bad_arg("theta is NULL");
+    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("obs_dim (3, 5, 7, 8 or 10)");
+    if (!obs) return bad_arg("obs is NULL");
+    if (!act) return bad_arg("act is NULL");
+    if (!old_logp) return bad_arg("old_logp is NULL");
+    if (!adv) return bad_arg("adv is NULL");
+    if (!ret) return bad_arg("ret is NULL");
+    if (!idx) return bad_arg("idx is NULL");
+    if (batch < 2) return bad_arg("batch < 2 (the advantages' standard deviation needs two rows)");
+    if (!workspace) return bad_arg("workspace is NULL");
+    if (!grad) return bad_arg("grad is NULL");
+    if (!stats) return bad_arg("stats is NULL");
+    hipError_t e = launch_ppo_grad(theta, obs_dim, obs, act, old_logp, adv, ret, idx, batch, clip_range, ent_coef, vf_coef,
+                                   workspace, grad, stats, (hipStream_t)stream);
+    return e == hipSuccess ? 0 : fail(e, "b747_ppo_grad");
+}
+
+__attribute__((visibility("default"))) int32_t b747_ppo_adam(float *theta, float *m, float *v, int64_t *t,
+                                                              const float *grad, int64_t n_params, double grad_scale,
+                                                              double max_grad_norm, double lr, double beta1, double beta2,
+                                                              double eps, void *stream)
+{
+    if (!theta) return bad_arg("theta is NULL");
+    if (!m) return bad_arg("m is NULL");
+    if (!v) return bad_arg("v is NULL");
+    if (!t) return bad_arg("t is NULL");
+    if (!grad) return bad_arg("grad is NULL");
+    if (n_params < 1) return bad_arg("n_params < 1");
+    hipError_t e = launch_ppo_adam(theta, m, v, t, grad, n_params, grad_scale, max_grad_norm, lr, beta1, beta2, eps,
+                                   (hipStream_t)stream);
+    return e == hipSuccess ? 0 : fail(e, "b747_ppo_adam");
 }
 
 __attribute__((visibility("default"))) int32_t b747_consts_default(b747_consts *c)

@@ -1,0 +1,64 @@
+// b747_ppo_update.hip -- the fused PPO minibatch update (b747_ppo_update.h): its kernels and their launchers, a
+// translation unit of their own so that the kernels of the other units keep their generated code.
+#define B747_POLICY_NO_KERNELS   // PolicyLayout only
+#include "b747_ppo_update.h"
+
+namespace b747 {
+
+namespace {
+
+template <int OD>
+hipError_t grad_od(const float *theta, const float *obs, const float *act, const float *old_logp, const float *adv,
+                   const float *ret, const int64_t *idx, int64_t batch, double clip_range, double ent_coef,
+                   double vf_coef, void *workspace, float *grad, float *stats, hipStream_t s)
+{
+    // (per call: the attribute belongs to the current device's copy of the kernel; a host-side setting, no stream work)
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ppo_grad<OD>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, UpdLds<OD>::bytes);
+    if (attr != hipSuccess) return attr;
+    constexpr int P = PolicyLayout::of(OD).total;
+    char *ws = static_cast<char *>(workspace);
+    double *adv_part = reinterpret_cast<double *>(ws + upd_ws_adv());
+    double *spart = reinterpret_cast<double *>(ws + upd_ws_sums());
+    float *gpart = reinterpret_cast<float *>(ws + upd_ws_grad());
+    const int64_t tiles = (batch + kUpdTile - 1) / kUpdTile, want = (tiles + 1) / 2;   // (two tiles in flight per workgroup and net)
+    const int n_wg = (int)(want < kUpdMaxWG ? want : kUpdMaxWG);
+    hipLaunchKernelGGL(k_ppo_adv_stats, dim3(kUpdAdvBlocks), dim3(256), 0, s, adv, idx, batch, adv_part);
+    hipLaunchKernelGGL(k_ppo_grad<OD>, dim3(n_wg), dim3(256), UpdLds<OD>::bytes, s, theta, obs, act, old_logp, adv, ret,
+                       idx, batch, clip_range, vf_coef, adv_part, gpart, spart);
+    hipLaunchKernelGGL(k_ppo_reduce, dim3((P + 1 + 255) / 256), dim3(256), 0, s, gpart, spart, n_wg, P,
+                       PolicyLayout::of(OD).ba, PolicyLayout::of(OD).bv, PolicyLayout::of(OD).log_std, theta, batch, (float)ent_coef, (float)vf_coef, grad, stats);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_ppo_grad(const float *theta, int od, const float *obs, const float *act, const float *old_logp,
+                           const float *adv, const float *ret, const int64_t *idx, int64_t batch, double clip_range,
+                           double ent_coef, double vf_coef, void *workspace, float *grad, float *stats, hipStream_t s)
+{
+#define B747_GRAD(OD)                                                                                              \
+    case OD:                                                                                                       \
+        return grad_od<OD>(theta, obs, act, old_logp, adv, ret, idx, batch, clip_range, ent_coef, vf_coef, workspace, \
+                           grad, stats, s)
+    switch (od) {
+        B747_GRAD(3);
+        B747_GRAD(5);
+        B747_GRAD(7);
+        B747_GRAD(8);
+        B747_GRAD(10);
+    default: return hipErrorInvalidValue;
+    }
+#undef B747_GRAD
+}
+
+hipError_t launch_ppo_adam(float *theta, float *m, float *v, int64_t *t, const float *grad, int64_t n_params,
+                           double grad_scale, double max_grad_norm, double lr, double beta1, double beta2, double eps,
+                           hipStream_t s)
+{
+    hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(kUpdAdamBlock), 0, s, theta, m, v, t, grad, n_params, grad_scale,
+                       max_grad_norm, lr, beta1, beta2, eps);
+    return hipGetLastError();
+}
+
+}  // namespace b747

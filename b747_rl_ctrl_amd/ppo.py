@@ -53,7 +53,7 @@ class ActorCritic(nn.Module):
                     nn.init.orthogonal_(lin.weight, gain=g)
                     nn.init.zeros_(lin.bias)
 
-    def flat_params(self):
+    def flat_param_list(self):
         """The parameters in the order b747_policy_act reads them (include/b747.h): pi_net layers,
         vf_net layers, action_net, value_net (weight then bias each), log_std."""
         seq = []
@@ -63,7 +63,11 @@ class ActorCritic(nn.Module):
                     seq += [lin.weight, lin.bias]
         seq += [self.action_net.weight, self.action_net.bias, self.value_net.weight, self.value_net.bias,
                 self.log_std]
-        return torch.cat([p.detach().reshape(-1) for p in seq])
+        return seq
+
+    def flat_params(self):
+        """flat_param_list() as one vector."""
+        return torch.cat([p.detach().reshape(-1) for p in self.flat_param_list()])
 
     def forward(self, obs):
         mean = self.action_net(self.pi_net(obs))
@@ -157,7 +161,8 @@ class PPO:
     """Device-resident PPO on a BatchControllerEnv (action space [-1, 1] with norm_act)."""
 
     def __init__(self, env: BatchControllerEnv, cfg: Optional[PPOConfig] = None, seed: int = 0, fused: bool = True,
-                 rollout_kernel: Optional[bool] = None, process_group=None, data_parallel: Optional[bool] = None):
+                 rollout_kernel: Optional[bool] = None, process_group=None, data_parallel: Optional[bool] = None,
+                 fused_update: bool = False):
         """fused=True: one b747_policy_act launch per rollout step (HIP kernel, include/b747.h);
         fused=False: the same policy as torch modules (reference implementation of the math).
         rollout_kernel (fused only; None = wherever it applies): the whole rollout as ONE
@@ -165,9 +170,17 @@ class PPO:
         configuration that kernel covers; False keeps two launches per step.
         data_parallel (None = whenever torch.distributed is initialised with more than one rank):
         average the gradients over `process_group` (module docstring); every rank must hold an env
-        shard of the same size so that all ranks run the same number of minibatches."""
+        shard of the same size so that all ranks run the same number of minibatches.
+        fused_update (needs fused=True; default False = the torch update, SB3-exact): train() runs every minibatch
+        step as b747_ppo_grad + b747_ppo_adam (loss, gradient, clip and Adam in HIP kernels on the flat parameter
+        vector, include/b747.h) instead of torch autograd and torch.optim.Adam; held to the torch path within
+        fp32 summation order (tests/test_gpu_ppo_update.py).  It keeps its own Adam moments and step count
+        (upd_m, upd_v, upd_t) and leaves self.opt alone."""
         self.env, self.cfg = env, cfg or PPOConfig()
         self.fused, self.seed = bool(fused), int(seed)
+        self.fused_update = bool(fused_update)
+        if self.fused_update and not self.fused:
+            raise ValueError("fused_update=True needs fused=True (the flat parameter buffer of the HIP policy)")
         dev, n, T, od = env.device, env.n, self.cfg.n_steps, env.obs_dim
         torch.manual_seed(seed)
         self.policy = ActorCritic(od).to(dev)
@@ -197,6 +210,14 @@ class PPO:
             self.flat = z(int(self._L.b747_policy_num_params(od)))
             self.step_base = torch.zeros(1, dtype=torch.int64, device=dev)   # Philox counter base
             self.sync_params()
+        if self.fused_update:
+            ws = int(self._L.b747_ppo_update_workspace(od))
+            if ws <= 0:
+                raise ValueError(f"fused_update does not cover this policy: {self._L.b747_last_error().decode()}")
+            self.n_params = sum(p.numel() for p in self.policy.flat_param_list())
+            self.upd_m, self.upd_v, self.upd_grad = z(self.n_params), z(self.n_params), z(self.n_params)
+            self.upd_t = torch.zeros(1, dtype=torch.int64, device=dev)       # Adam steps taken, advanced on the device
+            self.upd_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
         self.rollout_kernel = False
         if self.fused and rollout_kernel is not False:
             ok = self._ppo_rollout(0) == 0                # T = 0: validates the configuration, launches nothing
@@ -369,7 +390,8 @@ class PPO:
         views = (self.obs_buf[:T].reshape(N, -1), self.act_buf[:T].reshape(N, -1), self.logp_buf[:T].reshape(N),
                  self.adv_buf[:T].reshape(N), self.ret_buf[:T].reshape(N))
         n_mb = -(-N // c.batch_size)
-        rows = torch.empty(c.n_epochs * n_mb, 7, dtype=torch.float32, device=views[0].device)
+        # (the fused update writes its eight statistics, the loss last, straight into the row)
+        rows = torch.empty(c.n_epochs * n_mb, 8 if self.fused_update else 7, dtype=torch.float32, device=views[0].device)
         loss, k = None, 0
         for epoch in range(c.n_epochs):
             if minibatch_order is None:
@@ -378,9 +400,18 @@ class PPO:
                 perm = torch.as_tensor(minibatch_order(epoch, T, self.env.n), device=views[0].device)
             for i in range(0, N, c.batch_size):
                 idx = perm[i:i + c.batch_size]
-                loss, st = self._minibatch(idx, views)
-                rows[k].copy_(st)
+                if self.fused_update:
+                    loss = self._minibatch_fused(idx, rows[k])
+                else:
+                    loss, st = self._minibatch(idx, views)
+                    rows[k].copy_(st)
                 k += 1
+        if self.fused_update:       # the flat vector is the master copy during the epochs: hand it to the modules
+            with torch.no_grad():
+                off = 0
+                for prm in self.policy.flat_param_list():
+                    prm.copy_(self.flat[off:off + prm.numel()].view_as(prm))
+                    off += prm.numel()
         self.sync_params()
         with torch.no_grad():
             v, r = self.val_buf[:T].reshape(N), views[4]
@@ -421,6 +452,28 @@ class PPO:
         nn.utils.clip_grad_norm_(self.policy.parameters(), c.max_grad_norm)
         self.opt.step()
         return loss.detach(), st
+
+    def _minibatch_fused(self, idx, row):
+        """_minibatch as two stream-ordered calls on the flat parameter vector self.flat[:n_params] (no host
+        synchronisation): b747_ppo_grad gathers the rows `idx` from the time-major rollout buffers and writes the
+        gradient and the statistics row [.., loss]; b747_ppo_adam clips and steps.  Data-parallel: one all-reduce of
+        the flat gradient between them, its 1 / world folded into the Adam call.  Returns the loss (a view of row)."""
+        c, p = self.cfg, lambda x: x.data_ptr()
+        idx = idx.to(torch.int64).contiguous()
+        stream = torch.cuda.current_stream().cuda_stream
+        assert idx.numel() >= 2, "a minibatch of one row has no advantage standard deviation"
+        self._lib.check(self._L.b747_ppo_grad(
+            p(self.flat), self.env.obs_dim, p(self.obs_buf), p(self.act_buf), p(self.logp_buf), p(self.adv_buf),
+            p(self.ret_buf), p(idx), idx.numel(), c.clip_range, c.ent_coef, c.vf_coef, p(self.upd_ws), p(self.upd_grad),
+            p(row), stream), "b747_ppo_grad")
+        world = 1
+        if self.data_parallel and dist.is_available() and dist.is_initialized():
+            world = _world(self.group)
+            dist.all_reduce(self.upd_grad, op=dist.ReduceOp.SUM, group=self.group)
+        self._lib.check(self._L.b747_ppo_adam(
+            p(self.flat), p(self.upd_m), p(self.upd_v), p(self.upd_t), p(self.upd_grad), self.n_params, 1.0 / world,
+            c.max_grad_norm, c.learning_rate, 0.9, 0.999, 1e-5, stream), "b747_ppo_adam")
+        return row[7]
 
     def learn(self, iterations: int, n_steps: Optional[int] = None):
         T = n_steps or self.cfg.n_steps

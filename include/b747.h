@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define B747_ABI_VERSION 11  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
+#define B747_ABI_VERSION 12  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
                                 * 3: + b747_env_batch.rec_params, b747_struct_size; 4: + b747_env_batch.ep_stats;
                                 * 5: + b747_env_step_seq; 6: b747_model_batch.aero_err is double (the DLL's
                                 * `double aero_err[5]`, core/model.py:164), the policy buffer gains the layer-1
@@ -35,7 +35,8 @@ extern "C" {
                                 * the two-wave kernels run sample_time > dt (n_sub DLL steps per env step); 9: + b747_env_kernel,
                                 * and ep_return / ep_final_return accumulate as SB3's VecMonitor (float32); 10:
                                 * b747_ppo_rollout advances *step_base by T on the device, b747_env_batch.ep_return is float
-                                * (it holds float32 values; 8 B less per env step); 11: + b747_eval_episodes */
+                                * (it holds float32 values; 8 B less per env step); 11: + b747_eval_episodes;
+                                * 12: + b747_ppo_update_workspace, b747_ppo_grad, b747_ppo_adam */
 
 #define B747_NX 18   /* continuous states, SURVEY A.1 (dll.data@0x2b380) */
 #define B747_NDISC 9 /* compact discrete state, see b747_model_batch.disc */
@@ -343,6 +344,38 @@ int32_t b747_eval_episodes(const b747_env_batch *b, const b747_env_config *cfg, 
                            int32_t n_env_steps, int32_t sig_row, double scale, const double *y_base /* [N] */,
                            double error_band, float act_lo, float act_hi,
                            double *eval_out /* [B747_NEVAL][N] */, void *stream);
+
+/* ---- one PPO minibatch update on the device (b747_rl_ctrl_amd/ppo.py PPO._minibatch; SB3 1.4 PPO.train) ----
+ * For the policy of b747_policy_act (pi / vf nets obs_dim -> 64 -> 64 tanh, action_net, value_net, log_std; obs_dim 3, 5,
+ * 7, 8 or 10; one action).  theta = the first P = 128 obs_dim + 8579 floats of the policy buffer, in the order given
+ * above (b747_policy_pack is NOT needed between updates, only before the rollout kernels read the buffer again).
+ * Two calls per minibatch, so that a data-parallel all-reduce of the one flat gradient fits between them; both are
+ * stream-ordered and graph-capturable, allocate nothing, synchronise nothing and use no floating-point atomics: the
+ * same inputs give the same bits.  All pointers are device memory.
+ *
+ * b747_ppo_grad: for the rows r = idx[0 .. batch) (int64 row numbers t * N + i into the time-major rollout buffers
+ * obs [T*N][obs_dim], act, old_logp, adv, ret [T*N]) the loss
+ *   mean(-min(A ratio, A clamp(ratio, 1 - clip_range, 1 + clip_range))) + ent_coef (-entropy) + vf_coef mean((ret - value)^2)
+ * with A = (adv - mean) / (std + 1e-8) over the minibatch (unbiased std, fp64 sums) and ratio = exp(logp - old_logp);
+ * grad [P] = its gradient (flat_params order; where the clipped term is strictly smaller the row's policy gradient is
+ * 0); stats [8] = the policy-gradient loss, the value loss, the entropy loss, the clip fraction, approx_kl =
+ * mean((ratio - 1) - log ratio), mean |A ratio|, mean(|ratio| + 1 + |log ratio|), and the loss.  The forward in fp64, the
+ * backward products on the fp32 matrix cores (v_mfma_f32_32x32x2_f32: an fp32 fmaf chain), sums over rows in fp32 per
+ * workgroup and fp64 across them.  workspace: b747_ppo_update_workspace(obs_dim) bytes, 16-byte aligned, the caller's; its contents mean nothing
+ * between calls.  batch >= 2.
+ * b747_ppo_adam: g = grad_scale grad (1 / world for data-parallel ranks after a SUM all-reduce); coef = min(1,
+ * max_grad_norm / (|g|_2 + 1e-6)) (torch clip_grad_norm_); *t += 1; torch.optim.Adam's update of theta, m, v [n_params]
+ * with g coef (bias-corrected, no weight decay; PPO uses betas 0.9 / 0.999, eps 1e-5).  t: one device int64, the
+ * number of steps taken so far, advanced by the kernel.  grad is not modified.
+ * Both return -hipErrorInvalidValue, before anything reaches the device, for a NULL pointer, an obs_dim that
+ * b747_policy_act does not take, batch < 2 or n_params < 1 (b747_last_error names the argument). */
+int64_t b747_ppo_update_workspace(int32_t obs_dim);   /* bytes; -hipErrorInvalidValue for an unsupported obs_dim */
+int32_t b747_ppo_grad(const float *theta, int32_t obs_dim, const float *obs, const float *act, const float *old_logp,
+                      const float *adv, const float *ret, const int64_t *idx, int64_t batch, double clip_range,
+                      double ent_coef, double vf_coef, void *workspace, float *grad, float *stats, void *stream);
+int32_t b747_ppo_adam(float *theta, float *m, float *v, int64_t *t, const float *grad, int64_t n_params,
+                      double grad_scale, double max_grad_norm, double lr, double beta1, double beta2, double eps,
+                      void *stream);
 
 /* Human-readable text of the last error returned on this thread. */
 const char *b747_last_error(void);
