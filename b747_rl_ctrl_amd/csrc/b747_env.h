@@ -64,6 +64,29 @@ B747_HD double obs_max(int obs_type, int j)
  * the kernel-argument segment: scalar loads, no per-lane copy). */
 typedef b747_env_config EnvCfg;
 
+/* The reference's training configuration (main.py / env/ctrl_env.py defaults; BASELINE configs 3-5):
+ * PID_LIKE observation, CLASSIC reward, MANUAL control with DIRECT_CONTROL actions, CONST reference
+ * resets, AERO disturbance with drawn errors, normalised obs/action, no limiter, auto-reset.  Only the
+ * fields that select code paths are fixed; values (tk, limits, reward weights, seed, n_sub) stay
+ * run-time.  The kernels specialised on it overwrite their copy of the configuration with spec_config;
+ * spec_config_matches is the launch-time test for them (plan_env, b747_dispatch.h). */
+constexpr int kSpecObs = OBS_PID_LIKE, kSpecRew = REW_CLASSIC, kSpecLimiter = 0;
+B747_HD void spec_config(EnvCfg &c)
+{
+    c.obs_type = kSpecObs; c.reward_type = kSpecRew; c.ctrl_type = CT_MANUAL; c.ctrl_mode = CM_DIRECT;
+    c.reset_ref_mode = RM_CONST; c.disturbance_mode = 0; c.norm_obs = 1; c.norm_act = 1; c.use_limiter = kSpecLimiter;
+    c.auto_reset = 1; c.aero_fixed = 0;
+}
+B747_HD bool spec_config_matches(const EnvCfg &c)
+{
+    EnvCfg s = c;
+    spec_config(s);
+    return s.obs_type == c.obs_type && s.reward_type == c.reward_type && s.ctrl_type == c.ctrl_type &&
+           s.ctrl_mode == c.ctrl_mode && s.reset_ref_mode == c.reset_ref_mode && s.disturbance_mode == c.disturbance_mode &&
+           s.norm_obs == c.norm_obs && s.norm_act == c.norm_act && s.use_limiter == c.use_limiter &&
+           s.auto_reset == c.auto_reset && s.aero_fixed == c.aero_fixed;
+}
+
 /* ------------------------------------------------------------- Philox4x32-10 ---- */
 struct Rng {
     uint32_t k0, k1, c0, c1, c2, c3;   /* key = seed; counter = (env id, episode, block) */

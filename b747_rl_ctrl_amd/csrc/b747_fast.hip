@@ -16,78 +16,59 @@
 
 namespace b747 {
 
-void launch_env_steps_fast(const b747_env_batch &b, const b747_env_config &cfg, const Consts &C, int kind,
+static_assert(kSplitEnvs == kLargeWgEnvs && kBlock == kLargeWgEnvs && kMsEnvs == kSmallWgEnvs,
+              "the plans' workgroup sizes (b747_dispatch.h) are the kernels' defaults");
+
+bool launch_env_steps_fast(const b747_env_batch &b, const b747_env_config &cfg, const Consts &C, const EnvPlan &p,
                            const float *actions, int32_t n_env_steps, float *obs_seq, float *reward_seq,
                            uint8_t *done_seq, hipStream_t s)
 {
-    // the training configuration (kind 4): each env over a flight and a control wave.  MIXED: the same kernels with
-    // the flight aerodynamics in fp32 (include/b747.h B747_VARIANT_MIXED)
-    const bool mix = b.variant == B747_VARIANT_MIXED;
-    const dim3 grid((unsigned)((b.n + kSplitEnvs - 1) / kSplitEnvs));
-    if (kind == 4 && n_env_steps == 1 && cfg.n_sub == 1) {   // the per-step API (b747_split.h)
-        // 256 envs per workgroup (four wave triples, the three waves of a triple on one SIMD); small batches 64 (one
-        // triple: its three waves run on three SIMDs of a CU, and n / 64 CUs work instead of n / 256) -- faster up to
-        // 32,768 envs, slower at 65,536 (profiles/r06/small_batch_env_step.txt)
-        const bool small = b.n <= 32768;
-        const dim3 g64((unsigned)((b.n + 63) / 64));
-#define B747_STEP_SPLIT(XT, MIX) do { \
-            if (small) hipLaunchKernelGGL((k_env_step_split<XT, MIX, 64>), g64, dim3(3 * 64), 0, s, b.n, (const void *)b.X, \
-                                          (const double *)b.aero_err, (const uint32_t *)b.k, (const double *)b.disc, \
-                                          (const uint8_t *)b.flags, actions, b, cfg, obs_seq, reward_seq, done_seq); \
-            else hipLaunchKernelGGL((k_env_step_split<XT, MIX>), grid, dim3(kStepBlock), 0, s, b.n, (const void *)b.X, \
-                                    (const double *)b.aero_err, (const uint32_t *)b.k, (const double *)b.disc, \
-                                    (const uint8_t *)b.flags, actions, b, cfg, obs_seq, reward_seq, done_seq); \
-        } while (0)
-        if (b.x_f64) { if (mix) B747_STEP_SPLIT(double, true); else B747_STEP_SPLIT(double, false); }
-        else { if (mix) B747_STEP_SPLIT(float, true); else B747_STEP_SPLIT(float, false); }
-#undef B747_STEP_SPLIT
-        return;
+    // the training configuration: each env over a flight (and an ahead) and a control wave.  MIX: the same kernels with
+    // the flight aerodynamics in fp32 (include/b747.h B747_VARIANT_MIXED).  256 envs per workgroup (the waves of an env
+    // on one SIMD), or 64 (one wave per role, each on a SIMD of its own): plan_env, b747_dispatch.h
+    const bool small = p.envs_per_wg == kSmallWgEnvs;
+    if (p.kernel == EnvKernel::STEP_SPLIT) {   // the per-step API (b747_split.h)
+        with_bools([&](auto x64, auto mix, auto sm) {
+            constexpr int E = decltype(sm)::value ? kSmallWgEnvs : kSplitEnvs;
+            hipLaunchKernelGGL((k_env_step_split<storage_t<decltype(x64)>, decltype(mix)::value, E>), dim3(grid_for(b.n, E)),
+                               dim3(3 * E), 0, s, b.n, (const void *)b.X, (const double *)b.aero_err, (const uint32_t *)b.k,
+                               (const double *)b.disc, (const uint8_t *)b.flags, actions, b, cfg, obs_seq, reward_seq,
+                               done_seq);
+        }, p.x_f64, p.mix, small);
+        return true;
     }
-    if (kind == 4) {
+    if (p.kernel == EnvKernel::ROLLOUT_SPLIT) {
         // K steps per launch (b747_env_rollout), or one env step of n_sub > 1 DLL steps: the rollout kernel of
         // b747_ppo_rollout without the policy -- the two roles hand off per wave pair and the flight wave never waits
         // for the next step's controller (b747_ppo_split.h)
         const RolloutArgs ra{nullptr, 0, nullptr, actions, n_env_steps, obs_seq, nullptr, nullptr, reward_seq, done_seq,
                              0.0f, 0.0f, nullptr};
-        const bool sub = cfg.n_sub > 1;
-        // (small batches: one flight / control pair per 64-env workgroup, the two waves on two SIMDs, as the per-step
-        // kernel; faster up to 16,384 envs, slower from 24,576)
-        const bool small = b.n <= 16384;
-        const dim3 g64((unsigned)((b.n + 63) / 64));
-#define B747_ROLL(XT, SUB, MIX) do { \
-            if (small) hipLaunchKernelGGL((k_rollout_split<false, XT, SUB, MIX, 64>), g64, dim3(2 * 64), 0, s, b, cfg, ra); \
-            else hipLaunchKernelGGL((k_rollout_split<false, XT, SUB, MIX>), grid, dim3(kSplitBlock), 0, s, b, cfg, ra); \
-        } while (0)
-        if (b.x_f64) {
-            if (sub) { if (mix) B747_ROLL(double, true, true); else B747_ROLL(double, true, false); }
-            else { if (mix) B747_ROLL(double, false, true); else B747_ROLL(double, false, false); }
-        } else {
-            if (sub) { if (mix) B747_ROLL(float, true, true); else B747_ROLL(float, true, false); }
-            else { if (mix) B747_ROLL(float, false, true); else B747_ROLL(float, false, false); }
-        }
-#undef B747_ROLL
-        return;
+        with_bools([&](auto x64, auto sub, auto mix, auto sm) {
+            constexpr int E = decltype(sm)::value ? kSmallWgEnvs : kSplitEnvs;
+            hipLaunchKernelGGL((k_rollout_split<false, storage_t<decltype(x64)>, decltype(sub)::value, decltype(mix)::value, E>),
+                               dim3(grid_for(b.n, E)), dim3(2 * E), 0, s, b, cfg, ra);
+        }, p.x_f64, p.sub, p.mix, small);
+        return true;
     }
-    launch_env_steps<true>(b, cfg, C, kind == 4 ? 3 : kind, actions, n_env_steps, obs_seq, reward_seq, done_seq, s);
+    return launch_env_steps<true>(b, cfg, C, p, actions, n_env_steps, obs_seq, reward_seq, done_seq, s);
 }
 
-void launch_model_step_fast(const b747_model_batch &b, const Consts &C, int32_t n_steps, bool split, hipStream_t s)
+bool launch_model_step_fast(const b747_model_batch &b, const Consts &C, const ModelPlan &p, int32_t n_steps, hipStream_t s)
 {
     // the DLL's default constants: each env over three waves (b747_model_split.h) -- one step (BASELINE config 2's
-    // per-step calls), or K steps with the state in registers for small batches (config 2's 100-step launches; above
-    // 16,384 envs the one-wave kernel, whose single wave per env keeps every SIMD at one wave per 64 envs)
-    const dim3 g((unsigned)((b.n + kMsEnvs - 1) / kMsEnvs)), blk(kMsBlock);
-    if (split && n_steps == 1) {
-        if (b.x_f64) hipLaunchKernelGGL((k_model_step_split<double>), g, blk, 0, s, b);
-        else hipLaunchKernelGGL((k_model_step_split<float>), g, blk, 0, s, b);
-        return;
+    // per-step calls), or K steps with the state in registers for small batches (config 2's 100-step launches)
+    const dim3 g(grid_for(b.n, kMsEnvs)), blk(kMsBlock);
+    if (p.kernel == ModelKernel::STEP_SPLIT) {
+        with_bools([&](auto x64) { hipLaunchKernelGGL((k_model_step_split<storage_t<decltype(x64)>>), g, blk, 0, s, b); },
+                   p.x_f64);
+        return true;
     }
-    if (split && b.n <= 16384) {
-        if (b.x_f64) hipLaunchKernelGGL((k_model_steps_split<double>), g, blk, 0, s, b, n_steps);
-        else hipLaunchKernelGGL((k_model_steps_split<float>), g, blk, 0, s, b, n_steps);
-        return;
+    if (p.kernel == ModelKernel::STEPS_SPLIT) {
+        with_bools([&](auto x64) { hipLaunchKernelGGL((k_model_steps_split<storage_t<decltype(x64)>>), g, blk, 0, s, b, n_steps); },
+                   p.x_f64);
+        return true;
     }
-    launch_model_step<true>(b, C, n_steps, s);
+    return launch_model_step<true>(b, C, p, n_steps, s);
 }
 
 void launch_ppo_rollout_fast(const b747_env_batch &b, const b747_env_config &cfg, const float *params, uint64_t seed,
@@ -97,19 +78,14 @@ void launch_ppo_rollout_fast(const b747_env_batch &b, const b747_env_config &cfg
 {
     const RolloutArgs ra{params, seed, step_base, nullptr, T, obs_buf, act_buf, logp_buf, rew_buf, done_buf, act_lo, act_hi,
                          val_buf};
-    const dim3 grid((unsigned)((b.n + kSplitEnvs - 1) / kSplitEnvs));
-    const bool mix = b.variant == B747_VARIANT_MIXED;
-    const bool small = b.n <= 32768;   // (one flight / control pair per 64-env workgroup, as b747_env_rollout; the policy
-                                       //  then fits without spilling: faster up to 32,768 envs, slower at 65,536)
-    const dim3 g64((unsigned)((b.n + 63) / 64));
-#define B747_PPO(SUB, MIX) do { \
-        if (small) hipLaunchKernelGGL((k_rollout_split<true, double, SUB, MIX, 64>), g64, dim3(2 * 64), 0, s, b, cfg, ra); \
-        else hipLaunchKernelGGL((k_rollout_split<true, double, SUB, MIX>), grid, dim3(kSplitBlock), 0, s, b, cfg, ra); \
-    } while (0)
-    // sample_time > dt (main.py's 0.05): n_sub DLL steps per env step (core/controller.py:258-264)
-    if (cfg.n_sub > 1) { if (mix) B747_PPO(true, true); else B747_PPO(true, false); }
-    else { if (mix) B747_PPO(false, true); else B747_PPO(false, false); }
-#undef B747_PPO
+    // sub: sample_time > dt (main.py's 0.05), n_sub DLL steps per env step (core/controller.py:258-264); 64 envs per
+    // workgroup: one flight / control pair, as b747_env_rollout
+    const PpoPlan p = plan_ppo_rollout(b, cfg);
+    with_bools([&](auto sub, auto mix, auto sm) {
+        constexpr int E = decltype(sm)::value ? kSmallWgEnvs : kSplitEnvs;
+        hipLaunchKernelGGL((k_rollout_split<true, double, decltype(sub)::value, decltype(mix)::value, E>), dim3(grid_for(b.n, E)),
+                           dim3(2 * E), 0, s, b, cfg, ra);
+    }, p.sub, p.mix, p.envs_per_wg == kSmallWgEnvs);
 }
 
 }  // namespace b747

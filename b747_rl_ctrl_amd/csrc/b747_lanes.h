@@ -14,11 +14,13 @@
 #include "b747_dynamics.h"
 #include "b747_karg.h"
 #include "b747_env.h"
+#include "b747_dispatch.h"
 
 namespace b747 {
-// FAST launchers, defined in b747_fast.hip (hidden: not part of the C ABI)
-__attribute__((visibility("hidden"))) void launch_env_steps_fast(const b747_env_batch &b, const b747_env_config &cfg,
-                                                                 const Consts &C, int kind, const float *actions,
+// FAST launchers, defined in b747_fast.hip (hidden: not part of the C ABI).  Like launch_env_steps / launch_model_step
+// below they launch what the plan says and return false for a plan whose kernel their unit does not have.
+__attribute__((visibility("hidden"))) bool launch_env_steps_fast(const b747_env_batch &b, const b747_env_config &cfg,
+                                                                 const Consts &C, const EnvPlan &p, const float *actions,
                                                                  int32_t n_env_steps, float *obs_seq, float *reward_seq,
                                                                  uint8_t *done_seq, hipStream_t s);
 __attribute__((visibility("hidden"))) void launch_ppo_rollout_fast(const b747_env_batch &b, const b747_env_config &cfg,
@@ -27,8 +29,8 @@ __attribute__((visibility("hidden"))) void launch_ppo_rollout_fast(const b747_en
                                                                    float *act_buf, float *logp_buf, float *val_buf,
                                                                    float *rew_buf, uint8_t *done_buf, float act_lo,
                                                                    float act_hi, hipStream_t s);
-__attribute__((visibility("hidden"))) void launch_model_step_fast(const b747_model_batch &b, const Consts &C,
-                                                                  int32_t n_steps, bool split, hipStream_t s);
+__attribute__((visibility("hidden"))) bool launch_model_step_fast(const b747_model_batch &b, const Consts &C,
+                                                                  const ModelPlan &p, int32_t n_steps, hipStream_t s);
 }  // namespace b747
 
 namespace {
@@ -225,28 +227,6 @@ __global__ __launch_bounds__(kBlock) void k_model_init(b747_model_batch b, const
 
 
 // ------------------------------------------------------------------ env-level kernels ----
-
-// The reference's training configuration (main.py / env/ctrl_env.py defaults; BASELINE configs 3-5):
-// PID_LIKE observation, CLASSIC reward, MANUAL control with DIRECT_CONTROL actions, CONST reference
-// resets, AERO disturbance with drawn errors, normalised obs/action, no limiter, auto-reset.  Only the
-// fields that select code paths are fixed; values (tk, limits, reward weights, seed, n_sub) stay
-// run-time.  spec_config_matches is the launch-time test for kind 3.
-constexpr int kSpecObs = OBS_PID_LIKE, kSpecRew = REW_CLASSIC, kSpecLimiter = 0;
-__host__ __device__ __forceinline__ void spec_config(EnvCfg &c)
-{
-    c.obs_type = kSpecObs; c.reward_type = kSpecRew; c.ctrl_type = CT_MANUAL; c.ctrl_mode = CM_DIRECT;
-    c.reset_ref_mode = RM_CONST; c.disturbance_mode = 0; c.norm_obs = 1; c.norm_act = 1; c.use_limiter = kSpecLimiter;
-    c.auto_reset = 1; c.aero_fixed = 0;
-}
-inline bool spec_config_matches(const EnvCfg &c)
-{
-    EnvCfg s = c;
-    spec_config(s);
-    return s.obs_type == c.obs_type && s.reward_type == c.reward_type && s.ctrl_type == c.ctrl_type &&
-           s.ctrl_mode == c.ctrl_mode && s.reset_ref_mode == c.reset_ref_mode && s.disturbance_mode == c.disturbance_mode &&
-           s.norm_obs == c.norm_obs && s.norm_act == c.norm_act && s.use_limiter == c.use_limiter &&
-           s.auto_reset == c.auto_reset && s.aero_fixed == c.aero_fixed;
-}
 
 struct EnvLane {
     double x[NX];
@@ -605,47 +585,48 @@ __global__ __launch_bounds__(kBlock) void k_env_reset(b747_env_batch b, b747_env
     for (int j = 0; j < b.obs_dim; ++j) b.obs[i * b.obs_dim + j] = 0.0f;
 }
 
-inline unsigned grid_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+inline unsigned grid_for(int64_t n, int envs_per_wg = kBlock) { return (unsigned)((n + envs_per_wg - 1) / envs_per_wg); }
 
-// kind: 0 = generic constants, 1 = the DLL's defaults as literals, 2 = signal recording
+template <int K>
+using kind_c = std::integral_constant<int, K>;
+
+// The plan's one-wave env kernel (KIND and K1 above).  false: this unit has no kernel for the plan -- the split kernels
+// (b747_fast.hip launches those itself) and, in the FAITHFUL unit, the specialised kernel, which it never instantiates.
 template <bool FAST>
-void launch_env_steps(const b747_env_batch &b, const b747_env_config &cfg, const Consts &C, int kind,
+bool launch_env_steps(const b747_env_batch &b, const b747_env_config &cfg, const Consts &C, const EnvPlan &p,
                       const float *actions, int32_t n_env_steps, float *obs_seq, float *reward_seq, uint8_t *done_seq,
                       hipStream_t s)
 {
-    const dim3 g(grid_for(b.n)), blk(kBlock);
-#define B747_LAUNCH_ENV(XT, D) \
-    hipLaunchKernelGGL((k_env_steps<XT, FAST, D>), g, blk, 0, s, b, cfg, C, actions, n_env_steps, obs_seq, reward_seq, \
-                       done_seq)
-    const bool k1 = n_env_steps == 1 && cfg.n_sub == 1;
-#define B747_LAUNCH_ENV2(XT) \
-    if (kind == 2) B747_LAUNCH_ENV(XT, 2); \
-    else if (FAST && kind == 3 && k1) \
-        hipLaunchKernelGGL((k_env_steps<XT, FAST, (FAST ? 3 : 1), true>), g, blk, 0, s, b, cfg, C, actions, 1, obs_seq, \
-                           reward_seq, done_seq); \
-    else if (FAST && kind == 3) B747_LAUNCH_ENV(XT, (FAST ? 3 : 1)); \
-    else if (kind == 1) B747_LAUNCH_ENV(XT, 1); else B747_LAUNCH_ENV(XT, 0)
-    if (b.x_f64) B747_LAUNCH_ENV2(double);
-    else B747_LAUNCH_ENV2(float);
-#undef B747_LAUNCH_ENV2
-#undef B747_LAUNCH_ENV
+    return with_bools([&](auto x64) {
+        auto launch = [&](auto kind, auto k1) {
+            hipLaunchKernelGGL((k_env_steps<storage_t<decltype(x64)>, FAST, decltype(kind)::value, decltype(k1)::value>),
+                               dim3(grid_for(b.n)), dim3(kBlock), 0, s, b, cfg, C, actions, n_env_steps, obs_seq,
+                               reward_seq, done_seq);
+            return true;
+        };
+        switch (p.kernel) {
+        case EnvKernel::GENERIC: return launch(kind_c<0>{}, std::false_type{});
+        case EnvKernel::DEFC: return launch(kind_c<1>{}, std::false_type{});
+        case EnvKernel::RECORDING: return launch(kind_c<2>{}, std::false_type{});
+        case EnvKernel::SPEC_ONE_WAVE:
+            if constexpr (FAST) return with_bools([&](auto k1) { return launch(kind_c<3>{}, k1); }, p.k1);
+            return false;
+        default: return false;
+        }
+    }, p.x_f64);
 }
 
+// k_model_step with the plan's 64- or 256-lane workgroups; false for the three-wave kernels (b747_fast.hip)
 template <bool FAST>
-void launch_model_step(const b747_model_batch &b, const Consts &C, int32_t n_steps, hipStream_t s)
+bool launch_model_step(const b747_model_batch &b, const Consts &C, const ModelPlan &p, int32_t n_steps, hipStream_t s)
 {
-    // small batches (config 2: 4,096 envs): one wave per workgroup, so that the waves spread over n / 64 CUs instead of
-    // sharing n / 256 (each then has a CU's LDS, instruction and scalar caches to itself): 9.36 against 10.25 us per
-    // one-step launch at 4,096 envs, 5.30 against 5.38 us per step at 100 steps a launch (profiles/r06/config2_geometry.txt)
-    if (b.n <= 16384) {
-        const dim3 g((unsigned)((b.n + 63) / 64)), blk(64);
-        if (b.x_f64) hipLaunchKernelGGL((k_model_step<double, FAST, 64>), g, blk, 0, s, b, C, n_steps);
-        else hipLaunchKernelGGL((k_model_step<float, FAST, 64>), g, blk, 0, s, b, C, n_steps);
-        return;
-    }
-    const dim3 g(grid_for(b.n)), blk(kBlock);
-    if (b.x_f64) hipLaunchKernelGGL((k_model_step<double, FAST>), g, blk, 0, s, b, C, n_steps);
-    else hipLaunchKernelGGL((k_model_step<float, FAST>), g, blk, 0, s, b, C, n_steps);
+    if (p.kernel != ModelKernel::ONE_WAVE) return false;
+    with_bools([&](auto x64, auto small) {
+        constexpr int BS = decltype(small)::value ? kSmallWgEnvs : kBlock;
+        hipLaunchKernelGGL((k_model_step<storage_t<decltype(x64)>, FAST, BS>), dim3(grid_for(b.n, BS)), dim3(BS), 0, s, b, C,
+                           n_steps);
+    }, p.x_f64, p.envs_per_wg == kSmallWgEnvs);
+    return true;
 }
 
 }  // namespace
