@@ -24,6 +24,7 @@
 #include "b747_eval_args.h"
 #define B747_PPO_UPDATE_NO_KERNELS   // the update kernels live in b747_ppo_update.hip; this unit calls their launchers
 #include "b747_ppo_update.h"
+#include "b747_ppo_gae.h"
 
 using namespace b747;
 
@@ -260,6 +261,54 @@ B747_API int32_t b747_ppo_adam(float *theta, float *m, float *v, int64_t *t, con
                                                      beta2, eps, (hipStream_t)stream));
 }
 
+B747_API int32_t b747_ppo_gae(const float *rew, const float *val, const uint8_t *done, const float *last_value,
+                              int32_t T, int64_t N, double gamma, double gae_lambda, float *adv, float *ret,
+                              void *stream)
+{
+    if (!rew) return bad_arg("rew is NULL");
+    if (!val) return bad_arg("val is NULL");
+    if (!done) return bad_arg("done is NULL");
+    if (!last_value) return bad_arg("last_value is NULL");
+    if (!adv) return bad_arg("adv is NULL");
+    if (!ret) return bad_arg("ret is NULL");
+    if (T < 0) return bad_arg("T < 0");
+    if (N < 0) return bad_arg("N < 0");
+    if (N > (int64_t)kGaeBlock * INT32_MAX) return bad_arg("N (more envs than one grid holds)");
+    if (T == 0 || N == 0) return 0;
+    return launched("b747_ppo_gae",
+                    launch_ppo_gae(rew, val, done, last_value, T, N, gamma, gae_lambda, adv, ret, (hipStream_t)stream));
+}
+
+B747_API int32_t b747_ppo_epoch(float *theta, int32_t obs_dim, const float *obs, const float *act, const float *old_logp,
+                                const float *adv, const float *ret, const int64_t *perm, int64_t n_rows,
+                                int64_t batch_size, double clip_range, double ent_coef, double vf_coef, void *workspace,
+                                float *grad, float *m, float *v, int64_t *t, double max_grad_norm, double lr,
+                                double beta1, double beta2, double eps, float *stats, void *stream)
+{
+    if (!theta) return bad_arg("theta is NULL");
+    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("obs_dim (3, 5, 7, 8 or 10)");
+    if (!obs) return bad_arg("obs is NULL");
+    if (!act) return bad_arg("act is NULL");
+    if (!old_logp) return bad_arg("old_logp is NULL");
+    if (!adv) return bad_arg("adv is NULL");
+    if (!ret) return bad_arg("ret is NULL");
+    if (!perm) return bad_arg("perm is NULL");
+    if (n_rows < 2) return bad_arg("n_rows < 2 (the advantages' standard deviation needs two rows)");
+    if (batch_size < 2) return bad_arg("batch_size < 2 (the advantages' standard deviation needs two rows)");
+    if (n_rows % batch_size == 1)
+        return bad_arg("n_rows % batch_size == 1 (the last minibatch would be one row: no standard deviation)");
+    if (!workspace) return bad_arg("workspace is NULL");
+    if (!grad) return bad_arg("grad is NULL");
+    if (!m) return bad_arg("m is NULL");
+    if (!v) return bad_arg("v is NULL");
+    if (!t) return bad_arg("t is NULL");
+    if (!stats) return bad_arg("stats is NULL");
+    return launched("b747_ppo_epoch",
+                    launch_ppo_epoch(theta, obs_dim, obs, act, old_logp, adv, ret, perm, n_rows, batch_size, clip_range,
+                                     ent_coef, vf_coef, workspace, grad, m, v, t, max_grad_norm, lr, beta1, beta2, eps,
+                                     stats, (hipStream_t)stream));
+}
+
 B747_API int32_t b747_consts_default(b747_consts *c)
 {
     if (!c) return bad_arg("consts is NULL");
@@ -394,6 +443,8 @@ B747_API int32_t b747_set_specialization(int32_t on)
     g_spec = (on == 2) ? 2 : (on ? 1 : 0);
     return prev;
 }
+
+B747_API int32_t b747_get_specialization(void) { return g_spec; }
 
 B747_API int32_t b747_env_step(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c, void *stream)
 {

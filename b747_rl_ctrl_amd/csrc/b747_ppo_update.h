@@ -59,6 +59,13 @@ __attribute__((visibility("hidden"))) hipError_t launch_ppo_adam(float *theta, f
                                                                  const float *grad, int64_t n_params, double grad_scale,
                                                                  double max_grad_norm, double lr, double beta1,
                                                                  double beta2, double eps, hipStream_t s);
+// Every minibatch of one epoch (b747_ppo_epoch): launch_ppo_grad's launches on perm + j batch_size, then launch_ppo_adam
+// with grad_scale 1, for j = 0 .. ceil(n_rows / batch_size) - 1; the first launch error ends the loop and is returned
+__attribute__((visibility("hidden"))) hipError_t launch_ppo_epoch(
+    float *theta, int od, const float *obs, const float *act, const float *old_logp, const float *adv, const float *ret,
+    const int64_t *perm, int64_t n_rows, int64_t batch_size, double clip_range, double ent_coef, double vf_coef,
+    void *workspace, float *grad, float *m, float *v, int64_t *t, double max_grad_norm, double lr, double beta1,
+    double beta2, double eps, float *stats, hipStream_t s);
 
 #ifndef B747_PPO_UPDATE_NO_KERNELS
 

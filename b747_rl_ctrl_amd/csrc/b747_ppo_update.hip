@@ -7,15 +7,20 @@ namespace b747 {
 
 namespace {
 
+// (the attribute belongs to the current device's copy of the kernel; a host-side setting, no stream work)
 template <int OD>
-hipError_t grad_od(const float *theta, const float *obs, const float *act, const float *old_logp, const float *adv,
-                   const float *ret, const int64_t *idx, int64_t batch, double clip_range, double ent_coef,
-                   double vf_coef, void *workspace, float *grad, float *stats, hipStream_t s)
+hipError_t grad_lds_limit()
 {
-    // (per call: the attribute belongs to the current device's copy of the kernel; a host-side setting, no stream work)
-    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ppo_grad<OD>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, UpdLds<OD>::bytes);
-    if (attr != hipSuccess) return attr;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ppo_grad<OD>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, UpdLds<OD>::bytes);
+}
+
+// The three gradient launches of one minibatch (grad_lds_limit<OD>() has been called on this device)
+template <int OD>
+hipError_t grad_launch(const float *theta, const float *obs, const float *act, const float *old_logp, const float *adv,
+                       const float *ret, const int64_t *idx, int64_t batch, double clip_range, double ent_coef,
+                       double vf_coef, void *workspace, float *grad, float *stats, hipStream_t s)
+{
     constexpr int P = PolicyLayout::of(OD).total;
     char *ws = static_cast<char *>(workspace);
     double *adv_part = reinterpret_cast<double *>(ws + upd_ws_adv());
@@ -29,6 +34,38 @@ hipError_t grad_od(const float *theta, const float *obs, const float *act, const
     hipLaunchKernelGGL(k_ppo_reduce, dim3((P + 1 + 255) / 256), dim3(256), 0, s, gpart, spart, n_wg, P,
                        PolicyLayout::of(OD).ba, PolicyLayout::of(OD).bv, PolicyLayout::of(OD).log_std, theta, batch, (float)ent_coef, (float)vf_coef, grad, stats);
     return hipGetLastError();
+}
+
+template <int OD>
+hipError_t grad_od(const float *theta, const float *obs, const float *act, const float *old_logp, const float *adv,
+                   const float *ret, const int64_t *idx, int64_t batch, double clip_range, double ent_coef,
+                   double vf_coef, void *workspace, float *grad, float *stats, hipStream_t s)
+{
+    const hipError_t attr = grad_lds_limit<OD>();   // (per call)
+    if (attr != hipSuccess) return attr;
+    return grad_launch<OD>(theta, obs, act, old_logp, adv, ret, idx, batch, clip_range, ent_coef, vf_coef, workspace, grad,
+                           stats, s);
+}
+
+// b747_ppo_epoch's loop: minibatch j is grad_od's launches on perm + j batch_size and stats + 8 j, then
+// launch_ppo_adam with grad_scale 1 -- the launches of the two-call path in its order, the LDS limit raised once
+template <int OD>
+hipError_t epoch_od(float *theta, const float *obs, const float *act, const float *old_logp, const float *adv,
+                    const float *ret, const int64_t *perm, int64_t n_rows, int64_t batch_size, double clip_range,
+                    double ent_coef, double vf_coef, void *workspace, float *grad, float *m, float *v, int64_t *t,
+                    double max_grad_norm, double lr, double beta1, double beta2, double eps, float *stats, hipStream_t s)
+{
+    hipError_t e = grad_lds_limit<OD>();
+    if (e != hipSuccess) return e;
+    for (int64_t at = 0; at < n_rows; at += batch_size, stats += kUpdStats) {
+        const int64_t batch = n_rows - at < batch_size ? n_rows - at : batch_size;
+        e = grad_launch<OD>(theta, obs, act, old_logp, adv, ret, perm + at, batch, clip_range, ent_coef, vf_coef, workspace,
+                            grad, stats, s);
+        if (e != hipSuccess) return e;
+        e = launch_ppo_adam(theta, m, v, t, grad, PolicyLayout::of(OD).total, 1.0, max_grad_norm, lr, beta1, beta2, eps, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace
@@ -59,6 +96,27 @@ hipError_t launch_ppo_adam(float *theta, float *m, float *v, int64_t *t, const f
     hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(kUpdAdamBlock), 0, s, theta, m, v, t, grad, n_params, grad_scale,
                        max_grad_norm, lr, beta1, beta2, eps);
     return hipGetLastError();
+}
+
+hipError_t launch_ppo_epoch(float *theta, int od, const float *obs, const float *act, const float *old_logp,
+                            const float *adv, const float *ret, const int64_t *perm, int64_t n_rows, int64_t batch_size,
+                            double clip_range, double ent_coef, double vf_coef, void *workspace, float *grad, float *m,
+                            float *v, int64_t *t, double max_grad_norm, double lr, double beta1, double beta2,
+                            double eps, float *stats, hipStream_t s)
+{
+#define B747_EPOCH(OD)                                                                                               \
+    case OD:                                                                                                         \
+        return epoch_od<OD>(theta, obs, act, old_logp, adv, ret, perm, n_rows, batch_size, clip_range, ent_coef, vf_coef, \
+                            workspace, grad, m, v, t, max_grad_norm, lr, beta1, beta2, eps, stats, s)
+    switch (od) {
+        B747_EPOCH(3);
+        B747_EPOCH(5);
+        B747_EPOCH(7);
+        B747_EPOCH(8);
+        B747_EPOCH(10);
+    default: return hipErrorInvalidValue;
+    }
+#undef B747_EPOCH
 }
 
 }  // namespace b747

@@ -162,7 +162,7 @@ class PPO:
 
     def __init__(self, env: BatchControllerEnv, cfg: Optional[PPOConfig] = None, seed: int = 0, fused: bool = True,
                  rollout_kernel: Optional[bool] = None, process_group=None, data_parallel: Optional[bool] = None,
-                 fused_update: bool = False):
+                 fused_update: bool = False, gae_kernel: Optional[bool] = None, epoch_call: Optional[bool] = None):
         """fused=True: one b747_policy_act launch per rollout step (HIP kernel, include/b747.h);
         fused=False: the same policy as torch modules (reference implementation of the math).
         rollout_kernel (fused only; None = wherever it applies): the whole rollout as ONE
@@ -175,7 +175,14 @@ class PPO:
         step as b747_ppo_grad + b747_ppo_adam (loss, gradient, clip and Adam in HIP kernels on the flat parameter
         vector, include/b747.h) instead of torch autograd and torch.optim.Adam; held to the torch path within
         fp32 summation order (tests/test_gpu_ppo_update.py).  It keeps its own Adam moments and step count
-        (upd_m, upd_v, upd_t) and leaves self.opt alone."""
+        (upd_m, upd_v, upd_t) and leaves self.opt alone.
+        gae_kernel (None = wherever fused=True and the buffers are on the GPU): compute_gae's recurrence as ONE
+        b747_ppo_gae launch instead of the torch loop over the steps; the same bits (tests/test_gpu_ppo_gae.py).  True
+        raises where it cannot apply.
+        epoch_call (None = wherever fused_update=True and not data-parallel): train() runs each epoch's minibatches
+        as ONE b747_ppo_epoch call instead of two calls per minibatch from the interpreter; the same launches, the same
+        bits (tests/test_gpu_ppo_epoch.py).  True raises otherwise: data-parallel training keeps the two calls, its
+        all-reduce sits between them."""
         self.env, self.cfg = env, cfg or PPOConfig()
         self.fused, self.seed = bool(fused), int(seed)
         self.fused_update = bool(fused_update)
@@ -186,6 +193,12 @@ class PPO:
         self.policy = ActorCritic(od).to(dev)
         self.group = process_group
         self.data_parallel = (_world(process_group) > 1) if data_parallel is None else bool(data_parallel)
+        if epoch_call and not self.fused_update:
+            raise ValueError("epoch_call=True needs fused_update=True (b747_ppo_epoch runs the fused minibatch update)")
+        if epoch_call and self.data_parallel:
+            raise ValueError("epoch_call=True is single-rank only: data-parallel training all-reduces the gradient "
+                             "between b747_ppo_grad and b747_ppo_adam, which one b747_ppo_epoch call leaves no room for")
+        self.epoch_call = (self.fused_update and not self.data_parallel) if epoch_call is None else bool(epoch_call)
         if self.data_parallel:
             check_env_shards(env, process_group)
             broadcast_parameters(self.policy, process_group)
@@ -218,6 +231,10 @@ class PPO:
             self.upd_m, self.upd_v, self.upd_grad = z(self.n_params), z(self.n_params), z(self.n_params)
             self.upd_t = torch.zeros(1, dtype=torch.int64, device=dev)       # Adam steps taken, advanced on the device
             self.upd_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
+        gae_ok = self.fused and torch.device(dev).type == "cuda"
+        if gae_kernel and not gae_ok:
+            raise ValueError("gae_kernel=True needs fused=True and the rollout buffers on the GPU (b747_ppo_gae)")
+        self.gae_kernel = gae_ok if gae_kernel is None else bool(gae_kernel)
         self.rollout_kernel = False
         if self.fused and rollout_kernel is not False:
             ok = self._ppo_rollout(0) == 0                # T = 0: validates the configuration, launches nothing
@@ -305,9 +322,7 @@ class PPO:
         e.g. track_episodes / record_signals), the configuration and constants, and the kernel specialisation -- a
         change of any of them re-captures instead of replaying stale arguments"""
         from . import _lib
-        env, L = self.env, _lib.lib()
-        spec = int(L.b747_set_specialization(1))   # (the ABI has no query: read it by setting, then restore)
-        L.b747_set_specialization(spec)
+        env, spec = self.env, int(_lib.lib().b747_get_specialization())
         return (T, env._batch(), bytes(env.cfg), bytes(env.consts), spec)   # (the descriptor itself: no id reuse)
 
     def collect_rollouts(self, n_steps: Optional[int] = None, use_graph: bool = True):
@@ -357,10 +372,18 @@ class PPO:
 
     @torch.no_grad()
     def compute_gae(self, T: Optional[int] = None):
-        """Generalized advantage estimation (SB3 RolloutBuffer.compute_returns_and_advantage)."""
+        """Generalized advantage estimation (SB3 RolloutBuffer.compute_returns_and_advantage).  The bootstrap value is
+        one torch forward; the recurrence is one b747_ppo_gae launch over the first T rows (gae_kernel) or the torch
+        loop below, whose operation order the kernel keeps: both give the same bits."""
         T = T or self.cfg.n_steps
         c = self.cfg
         _, last_value = self.policy(self._bootstrap_obs())
+        if self.gae_kernel:
+            p, last_value = (lambda x: x.data_ptr()), last_value.contiguous()
+            self._lib.check(self._L.b747_ppo_gae(
+                p(self.rew_buf), p(self.val_buf), p(self.done_buf), p(last_value), T, self.env.n, c.gamma, c.gae_lambda,
+                p(self.adv_buf), p(self.ret_buf), torch.cuda.current_stream().cuda_stream), "b747_ppo_gae")
+            return
         gae = torch.zeros_like(last_value)
         for t in reversed(range(T)):
             next_value = last_value if t == T - 1 else self.val_buf[t + 1]
@@ -398,6 +421,10 @@ class PPO:
                 perm = torch.randperm(N, device=views[0].device)
             else:
                 perm = torch.as_tensor(minibatch_order(epoch, T, self.env.n), device=views[0].device)
+            if self.epoch_call:     # every minibatch of the epoch from one C call, the statistics straight into rows
+                loss = self._epoch_fused(perm, N, rows[k:k + n_mb])
+                k += n_mb
+                continue
             for i in range(0, N, c.batch_size):
                 idx = perm[i:i + c.batch_size]
                 if self.fused_update:
@@ -474,6 +501,20 @@ class PPO:
             p(self.flat), p(self.upd_m), p(self.upd_v), p(self.upd_t), p(self.upd_grad), self.n_params, 1.0 / world,
             c.max_grad_norm, c.learning_rate, 0.9, 0.999, 1e-5, stream), "b747_ppo_adam")
         return row[7]
+
+    def _epoch_fused(self, perm, N, rows):
+        """The minibatch loop of one epoch over the sample order `perm` as one b747_ppo_epoch call: per minibatch the
+        launches of _minibatch_fused, from a C loop (single rank).  rows [n_mb][8] receives the statistics.  Returns
+        the last minibatch's loss (a view of rows)."""
+        c, p = self.cfg, lambda x: x.data_ptr()
+        perm = perm.to(torch.int64).contiguous()
+        assert perm.numel() == N, "minibatch_order must give every row of the rollout once"
+        self._lib.check(self._L.b747_ppo_epoch(
+            p(self.flat), self.env.obs_dim, p(self.obs_buf), p(self.act_buf), p(self.logp_buf), p(self.adv_buf),
+            p(self.ret_buf), p(perm), N, c.batch_size, c.clip_range, c.ent_coef, c.vf_coef, p(self.upd_ws),
+            p(self.upd_grad), p(self.upd_m), p(self.upd_v), p(self.upd_t), c.max_grad_norm, c.learning_rate, 0.9, 0.999,
+            1e-5, p(rows), torch.cuda.current_stream().cuda_stream), "b747_ppo_epoch")
+        return rows[-1, 7]
 
     def learn(self, iterations: int, n_steps: Optional[int] = None):
         T = n_steps or self.cfg.n_steps

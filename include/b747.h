@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define B747_ABI_VERSION 12  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
+#define B747_ABI_VERSION 13  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
                                 * 3: + b747_env_batch.rec_params, b747_struct_size; 4: + b747_env_batch.ep_stats;
                                 * 5: + b747_env_step_seq; 6: b747_model_batch.aero_err is double (the DLL's
                                 * `double aero_err[5]`, core/model.py:164), the policy buffer gains the layer-1
@@ -36,7 +36,8 @@ extern "C" {
                                 * and ep_return / ep_final_return accumulate as SB3's VecMonitor (float32); 10:
                                 * b747_ppo_rollout advances *step_base by T on the device, b747_env_batch.ep_return is float
                                 * (it holds float32 values; 8 B less per env step); 11: + b747_eval_episodes;
-                                * 12: + b747_ppo_update_workspace, b747_ppo_grad, b747_ppo_adam */
+                                * 12: + b747_ppo_update_workspace, b747_ppo_grad, b747_ppo_adam; 13: + b747_ppo_gae,
+                                * b747_ppo_epoch, b747_get_specialization */
 
 #define B747_NX 18   /* continuous states, SURVEY A.1 (dll.data@0x2b380) */
 #define B747_NDISC 9 /* compact discrete state, see b747_model_batch.disc */
@@ -268,6 +269,8 @@ int32_t b747_env_time_steps(const b747_env_batch *b, const b747_env_config *cfg,
  * b747_model_step call on the one-wave kernel.
  * Returns the previous setting.  No reference counterpart (the reference has no kernels). */
 int32_t b747_set_specialization(int32_t on);
+/* The current setting (0, 1 or 2: what b747_set_specialization last set, 1 at load); changes nothing (ABI 13). */
+int32_t b747_get_specialization(void);
 
 /* Which kernel b747_env_rollout(b, cfg, c, ..., n_env_steps) launches for this batch and configuration (b747_env_step
  * is n_env_steps = 1): B747_KERNEL_* below.  Lets a caller (and the tests) confirm that a configuration runs the
@@ -376,6 +379,39 @@ int32_t b747_ppo_grad(const float *theta, int32_t obs_dim, const float *obs, con
 int32_t b747_ppo_adam(float *theta, float *m, float *v, int64_t *t, const float *grad, int64_t n_params,
                       double grad_scale, double max_grad_norm, double lr, double beta1, double beta2, double eps,
                       void *stream);
+
+/* ---- every minibatch of one PPO epoch from one call (ABI 13; PPO.train's inner loop) ----
+ * For j = 0 .. ceil(n_rows / batch_size) - 1: the launches of b747_ppo_grad with idx = perm + j batch_size, batch =
+ * min(batch_size, n_rows - j batch_size) and stats + 8 j, then those of b747_ppo_adam with grad_scale 1 and n_params = P
+ * -- the same kernels with the same arguments in the same order as the two calls in a host loop, so the same bits; the
+ * host work per minibatch is four launches and nothing else (the gradient kernel's LDS limit is raised once per call).
+ * perm [n_rows]: int64 row numbers into the rollout buffers (one epoch's permutation); stats [ceil(n_rows /
+ * batch_size)][8], one row per minibatch.  Single rank only: a data-parallel all-reduce belongs between the two calls
+ * of the two-call path.  Everything is validated before the first launch: the checks of b747_ppo_grad and
+ * b747_ppo_adam, n_rows >= 2, batch_size >= 2, and n_rows % batch_size != 1 (a last minibatch of one row has no
+ * advantage standard deviation); -hipErrorInvalidValue with the argument named in b747_last_error.  If a launch fails
+ * at minibatch j the call returns that error at once and minibatches 0 .. j-1 stay applied to theta, m, v and *t.
+ * Stream-ordered, graph-capturable (the capture then holds this perm's addresses), no allocation. */
+int32_t b747_ppo_epoch(float *theta, int32_t obs_dim, const float *obs, const float *act, const float *old_logp,
+                       const float *adv, const float *ret, const int64_t *perm, int64_t n_rows, int64_t batch_size,
+                       double clip_range, double ent_coef, double vf_coef, void *workspace, float *grad,
+                       float *m, float *v, int64_t *t, double max_grad_norm, double lr, double beta1, double beta2,
+                       double eps, float *stats /* [ceil(n_rows / batch_size)][8] */, void *stream);
+
+/* ---- generalized advantage estimation in one launch (ABI 13; PPO.compute_gae, SB3 1.4
+ * RolloutBuffer.compute_returns_and_advantage) ----
+ * rew, val, adv, ret [T][N] float and done [T][N] bytes (0 / 1), time-major (row t * N + i); last_value [N]: the value
+ * of the observation after the last step.  With g = (float)gamma and gl = (float)(gamma * gae_lambda) (the double
+ * product rounded once), per env a = 0 and for t = T-1 .. 0:
+ *   nv = t == T-1 ? last_value[i] : val[(t+1) N + i];   nt = done[t N + i] ? 0.f : 1.f;
+ *   delta = (rew + ((g * nv) * nt)) - val;   a = delta + ((gl * nt) * a);   adv[t N + i] = a;   ret[t N + i] = a + val
+ * -- one fp32 rounding per operation, in this order, with no FMA contraction: the operation sequence of the torch loop
+ * in PPO.compute_gae, whose results it reproduces bit for bit.  One lane per env.  adv and ret must not overlap rew,
+ * val, done or last_value (not detected).  A NULL pointer, T < 0 or N < 0 returns -hipErrorInvalidValue before
+ * anything reaches the device (b747_last_error names the argument); T == 0 or N == 0 returns 0 and launches nothing.
+ * Stream-ordered, graph-capturable, no allocation. */
+int32_t b747_ppo_gae(const float *rew, const float *val, const uint8_t *done, const float *last_value,
+                     int32_t T, int64_t N, double gamma, double gae_lambda, float *adv, float *ret, void *stream);
 
 /* Human-readable text of the last error returned on this thread. */
 const char *b747_last_error(void);
