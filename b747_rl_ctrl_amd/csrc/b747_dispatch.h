@@ -97,6 +97,20 @@ inline PpoPlan plan_ppo_rollout(const b747_env_batch &b, const b747_env_config &
                    b.n <= kPpoRolloutSmallMax ? kSmallWgEnvs : kLargeWgEnvs};
 }
 
+/* b747_ppo_rollout_lanes' one-wave kernel (k_rollout_lanes, b747_rollout_lanes.h) runs the generic lane code: every
+ * configuration, constants, variant (MIXED as FAST) and n >= 1 that b747_env_step covers.  What it does not cover, as
+ * the reason the entry point reports; NULL = covered. */
+inline const char *ppo_rollout_lanes_refusal(const b747_env_batch &b)
+{
+    if (b.obs_dim != 3 && b.obs_dim != 5)
+        return "b747_ppo_rollout_lanes: obs_dim (the one-wave rollout kernel runs a policy with PID_LIKE 3 or SPEED_MODE "
+               "5 only; use b747_policy_act + b747_env_step)";
+    if (!b.x_f64) return "b747_ppo_rollout_lanes: x_f64 (the one-wave rollout kernel keeps fp64 state only)";
+    if (b.sig) return "b747_ppo_rollout_lanes: sig (no per-DLL-step signal recording inside the rollout kernel)";
+    return nullptr;
+}
+inline bool ppo_rollout_lanes_covers(const b747_env_batch &b) { return ppo_rollout_lanes_refusal(b) == nullptr; }
+
 /* ------------------------------------------------------------------------- model step ---- */
 enum class ModelKernel : int32_t {
     ONE_WAVE = 0,      /* k_model_step: one wave per env, run-time constants */

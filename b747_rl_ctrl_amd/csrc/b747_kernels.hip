@@ -22,6 +22,8 @@
 #include "b747_lanes.h"
 #include "b747_policy.h"
 #include "b747_eval_args.h"
+#define B747_ROLLOUT_LANES_NO_KERNELS   // k_rollout_lanes lives in b747_rollout_lanes_{fast,faithful}.hip
+#include "b747_rollout_lanes.h"
 #define B747_PPO_UPDATE_NO_KERNELS   // the update kernels live in b747_ppo_update.hip; this unit calls their launchers
 #include "b747_ppo_update.h"
 #include "b747_ppo_gae.h"
@@ -190,6 +192,44 @@ B747_API int32_t b747_ppo_rollout(const b747_env_batch *b, const b747_env_config
     hipLaunchKernelGGL(k_policy_value<3>, dim3((unsigned)policy_value_blocks(rows)), dim3(256), 0, (hipStream_t)stream,
                        params, rows, obs_buf, val_buf, step_base, (uint32_t)T);
     return launched("b747_ppo_rollout");
+}
+
+B747_API int32_t b747_ppo_rollout_lanes(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c,
+                                        const float *params, uint64_t seed, uint64_t *step_base, int32_t T,
+                                        float *obs_buf, float *act_buf, float *logp_buf, float *val_buf, float *rew_buf,
+                                        uint8_t *done_buf, float act_lo, float act_hi, void *stream)
+{
+    int32_t r = check_env(b, cfg);
+    if (r < 0) return r;
+    if (!c) return bad_arg("b747_ppo_rollout_lanes: consts is NULL");
+    if (!params) return bad_arg("b747_ppo_rollout_lanes: params is NULL");
+    if (!obs_buf) return bad_arg("b747_ppo_rollout_lanes: obs_buf is NULL");
+    if (!act_buf) return bad_arg("b747_ppo_rollout_lanes: act_buf is NULL");
+    if (!logp_buf) return bad_arg("b747_ppo_rollout_lanes: logp_buf is NULL");
+    if (!val_buf) return bad_arg("b747_ppo_rollout_lanes: val_buf is NULL");
+    if (!rew_buf) return bad_arg("b747_ppo_rollout_lanes: rew_buf is NULL");
+    if (!done_buf) return bad_arg("b747_ppo_rollout_lanes: done_buf is NULL");
+    if (T < 0) return bad_arg("b747_ppo_rollout_lanes: T < 0");
+    if (!(act_lo <= act_hi)) return bad_arg("b747_ppo_rollout_lanes: act_lo > act_hi");
+    if (r == 0) return 0;   // an empty batch
+    if (const char *why = ppo_rollout_lanes_refusal(*b)) return bad_arg(why);
+    if (T == 0) return 0;
+    const RolloutLanesArgs ra{params, seed, step_base, T, act_lo, act_hi, obs_buf, act_buf, logp_buf, val_buf, rew_buf,
+                              done_buf};
+    const Consts C = consts_of(c);   // run-time constants, as the evaluation kernel
+    // (the launcher's second launch advances *step_base by T: ordered after the rollout kernel's last read of it;
+    //  where the value head is deferred, b747_ppo_rollout's value pass does both)
+    const bool defer = kLanesDeferValue3 && b->obs_dim == 3;
+    uint64_t *advance = defer ? nullptr : step_base;
+    if (b->variant != B747_VARIANT_FAITHFUL)
+        launch_rollout_lanes_fast(*b, *cfg, C, ra, b->obs_dim, advance, (hipStream_t)stream);
+    else launch_rollout_lanes_faithful(*b, *cfg, C, ra, b->obs_dim, advance, (hipStream_t)stream);
+    if (defer) {
+        const int64_t rows = (int64_t)T * b->n;
+        hipLaunchKernelGGL(k_policy_value<3>, dim3((unsigned)policy_value_blocks(rows)), dim3(256), 0,
+                           (hipStream_t)stream, params, rows, obs_buf, val_buf, step_base, (uint32_t)T);
+    }
+    return launched("b747_ppo_rollout_lanes");
 }
 
 B747_API int32_t b747_eval_episodes(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c,

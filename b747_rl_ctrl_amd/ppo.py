@@ -20,7 +20,7 @@ Adam step -- the only collective, once per minibatch, never on the rollout path.
 """
 import math
 from dataclasses import dataclass
-from typing import Callable, Optional
+from typing import Callable, Optional, Union
 
 import torch
 import torch.distributed as dist
@@ -161,13 +161,17 @@ class PPO:
     """Device-resident PPO on a BatchControllerEnv (action space [-1, 1] with norm_act)."""
 
     def __init__(self, env: BatchControllerEnv, cfg: Optional[PPOConfig] = None, seed: int = 0, fused: bool = True,
-                 rollout_kernel: Optional[bool] = None, process_group=None, data_parallel: Optional[bool] = None,
+                 rollout_kernel: Union[bool, str, None] = None, process_group=None, data_parallel: Optional[bool] = None,
                  fused_update: bool = False, gae_kernel: Optional[bool] = None, epoch_call: Optional[bool] = None):
         """fused=True: one b747_policy_act launch per rollout step (HIP kernel, include/b747.h);
         fused=False: the same policy as torch modules (reference implementation of the math).
         rollout_kernel (fused only; None = wherever it applies): the whole rollout as ONE
         b747_ppo_rollout launch (policy + env step fused, state in registers across steps) for the
-        configuration that kernel covers; False keeps two launches per step.
+        configuration that kernel covers; False keeps two launches per step.  "lanes" (opt-in, fused only): the
+        whole rollout as ONE b747_ppo_rollout_lanes launch for any configuration with a PID_LIKE or SPEED_MODE
+        observation and fp64 state -- one wave per 64 envs on the generic lane code, the env state in registers
+        across the steps; ValueError with the library's message where it does not apply (INTEGRATION.md says
+        when to pick it).
         data_parallel (None = whenever torch.distributed is initialised with more than one rank):
         average the gradients over `process_group` (module docstring); every rank must hold an env
         shard of the same size so that all ranks run the same number of minibatches.
@@ -236,7 +240,15 @@ class PPO:
             raise ValueError("gae_kernel=True needs fused=True and the rollout buffers on the GPU (b747_ppo_gae)")
         self.gae_kernel = gae_ok if gae_kernel is None else bool(gae_kernel)
         self.rollout_kernel = False
-        if self.fused and rollout_kernel is not False:
+        if isinstance(rollout_kernel, str):
+            if rollout_kernel != "lanes":
+                raise ValueError(f"rollout_kernel={rollout_kernel!r}: None, True, False or \"lanes\"")
+            if not self.fused:
+                raise ValueError("rollout_kernel=\"lanes\" needs fused=True (b747_ppo_rollout_lanes reads the packed policy)")
+            self.rollout_kernel = "lanes"
+            if self._ppo_rollout(0) != 0:                 # T = 0: validates the configuration, launches nothing
+                raise ValueError(f"b747_ppo_rollout_lanes does not cover this env: {self._L.b747_last_error().decode()}")
+        elif self.fused and rollout_kernel is not False:
             ok = self._ppo_rollout(0) == 0                # T = 0: validates the configuration, launches nothing
             if rollout_kernel and not ok:
                 raise ValueError(f"b747_ppo_rollout does not cover this env: {self._L.b747_last_error().decode()}")
@@ -294,12 +306,22 @@ class PPO:
         env.rollout(env.action.view(1, -1), None, self.rew_buf[t], self.done_buf[t])
 
     def _ppo_rollout(self, T: int) -> int:
+        """The rollout kernel's call (b747_ppo_rollout, or b747_ppo_rollout_lanes for rollout_kernel="lanes": the same
+        arguments); the library's return code."""
         env, p = self.env, lambda x: x.data_ptr()
-        env._batch()
-        return self._L.b747_ppo_rollout(env._bref, env._cref, env._kref, p(self.flat), self.seed, p(self.step_base), T,
-                                        p(self.obs_buf), p(self.act_buf), p(self.logp_buf), p(self.val_buf),
-                                        p(self.rew_buf), p(self.done_buf), self.act_lo, self.act_hi,
-                                        torch.cuda.current_stream().cuda_stream)
+        b = env._batch()
+        call = self._L.b747_ppo_rollout
+        if self.rollout_kernel == "lanes":
+            call = self._L.b747_ppo_rollout_lanes
+            b.action = p(env.action)      # the kernel leaves the last clipped action there (env.step may have pointed
+                                          # the descriptor at a caller's buffer)
+        return call(env._bref, env._cref, env._kref, p(self.flat), self.seed, p(self.step_base), T,
+                    p(self.obs_buf), p(self.act_buf), p(self.logp_buf), p(self.val_buf),
+                    p(self.rew_buf), p(self.done_buf), self.act_lo, self.act_hi,
+                    torch.cuda.current_stream().cuda_stream)
+
+    def _rollout_call_name(self) -> str:
+        return "b747_ppo_rollout_lanes" if self.rollout_kernel == "lanes" else "b747_ppo_rollout"
 
     def _end_rollout(self, T: int):
         if self.fused:
@@ -307,7 +329,7 @@ class PPO:
             self.last_obs.copy_(self.env.obs)         # bootstrap observation for GAE
 
     def _end_kernel_rollout(self):
-        # b747_ppo_rollout advances step_base itself (ABI 10), and the bootstrap observation is the env's, taken
+        # b747_ppo_rollout and b747_ppo_rollout_lanes advance step_base themselves (ABI 10, 14), and the bootstrap observation is the env's, taken
         # when compute_gae needs it: the captured rollout is then its two kernels and nothing else
         self._last_obs_from_env = True
 
@@ -333,7 +355,7 @@ class PPO:
         if self.rollout_kernel:                      # one launch for the whole rollout
             if not use_graph:
                 with torch.no_grad():
-                    self._lib.check(self._ppo_rollout(T), "b747_ppo_rollout")
+                    self._lib.check(self._ppo_rollout(T), self._rollout_call_name())
                 self._end_kernel_rollout()
                 return T
             # ... and with use_graph, that launch and the value pass replayed as one HIP graph: no host work between
@@ -344,7 +366,7 @@ class PPO:
                 s.wait_stream(torch.cuda.current_stream())
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, stream=s), torch.no_grad():
-                    self._lib.check(self._ppo_rollout(T), "b747_ppo_rollout")
+                    self._lib.check(self._ppo_rollout(T), self._rollout_call_name())
                 self._graph, self._graph_steps = g, self._graph_key(T)
             self._graph.replay()
             self._end_kernel_rollout()

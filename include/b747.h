@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define B747_ABI_VERSION 13  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
+#define B747_ABI_VERSION 14  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
                                 * 3: + b747_env_batch.rec_params, b747_struct_size; 4: + b747_env_batch.ep_stats;
                                 * 5: + b747_env_step_seq; 6: b747_model_batch.aero_err is double (the DLL's
                                 * `double aero_err[5]`, core/model.py:164), the policy buffer gains the layer-1
@@ -37,7 +37,7 @@ extern "C" {
                                 * b747_ppo_rollout advances *step_base by T on the device, b747_env_batch.ep_return is float
                                 * (it holds float32 values; 8 B less per env step); 11: + b747_eval_episodes;
                                 * 12: + b747_ppo_update_workspace, b747_ppo_grad, b747_ppo_adam; 13: + b747_ppo_gae,
-                                * b747_ppo_epoch, b747_get_specialization */
+                                * b747_ppo_epoch, b747_get_specialization; 14: + b747_ppo_rollout_lanes */
 
 #define B747_NX 18   /* continuous states, SURVEY A.1 (dll.data@0x2b380) */
 #define B747_NDISC 9 /* compact discrete state, see b747_model_batch.disc */
@@ -313,6 +313,28 @@ int32_t b747_ppo_rollout(const b747_env_batch *b, const b747_env_config *cfg, co
                          uint64_t seed, uint64_t *step_base, int32_t T, float *obs_buf, float *act_buf,
                          float *logp_buf, float *val_buf, float *rew_buf, uint8_t *done_buf, float act_lo, float act_hi,
                          void *stream);
+/* The same T rollout steps in ONE launch for every other env (ABI 14): the arguments of b747_ppo_rollout, with
+ * obs_buf [T][N][obs_dim].  Each env on one lane of a one-wave workgroup (64 envs per wave, any N >= 1): the policy
+ * with both heads, b747_policy_act's Philox sample (seed, env_offset + i, *step_base + t), log-prob and clip, then the
+ * generic lane code of b747_env_step -- every control type / mode, reward, reset mode, disturbance, limiter setting and
+ * n_sub, run-time constants, FAST or FAITHFUL arithmetic (MIXED runs FAST) -- with the env state and the observation
+ * in registers across the T steps.  Row t*N + i of obs_buf (the observation the policy saw), act_buf (unclipped),
+ * logp_buf, val_buf, rew_buf, done_buf.  An episode that ends is booked and, with cfg->auto_reset, reset as
+ * b747_env_step does it (terminal_obs, ep_final_*, ep_stats, state0); afterwards the env -- state, obs, reward, done,
+ * action (where non-NULL: the last clipped action) -- is what T calls of b747_policy_act + b747_env_step would have
+ * left: bit for bit in FAITHFUL, within the FAST kernels' contraction otherwise (tests/test_gpu_ppo_rollout_lanes.py).
+ * A second launch then advances *step_base (device, nullable = 0) by T, so that consecutive calls -- or replays of
+ * one captured graph -- draw fresh noise: for obs_dim 3 it is b747_ppo_rollout's batched value pass over the T*N rows
+ * of obs_buf, which writes val_buf (the value head is then not in the step loop); for obs_dim 5, whose value head
+ * runs in the loop, a one-thread launch.  Returns -hipErrorInvalidValue, with the reason in
+ * b747_last_error, for an obs_dim other than 3 / 5 (PID_LIKE / SPEED_MODE: the matrix-core policy of the evaluation
+ * kernel), fp32 state (x_f64 == 0), a batch that records signals (b->sig), a NULL buffer, T < 0 or act_lo > act_hi;
+ * b747_ppo_rollout keeps refusing what it refused before.  T == 0 validates and launches nothing.  Stream-ordered,
+ * graph-capturable, no allocation. */
+int32_t b747_ppo_rollout_lanes(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c,
+                               const float *params, uint64_t seed, uint64_t *step_base, int32_t T, float *obs_buf,
+                               float *act_buf, float *logp_buf, float *val_buf, float *rew_buf, uint8_t *done_buf,
+                               float act_lo, float act_hi, void *stream);
 int32_t b747_policy_pack(float *params, int32_t obs_dim, void *stream);
 /* noise [N] (nullable): standard-normal draws; NULL = Philox4x32-10 keyed by seed with counter
  * (env_offset + i, *step_base + step); step_base (device, nullable = 0) lets a captured rollout
