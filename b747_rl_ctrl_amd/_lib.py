@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # B747_LIB_PATH: an A/B build to load instead of the product library (tools/ab_*.sh); the product .so is never
 # overwritten by a variant, so an interrupted A/B run cannot leave one in its place
 LIB_PATH = os.environ.get("B747_LIB_PATH") or os.path.join(HERE, "libb747.so")
-ABI_VERSION = 14        # include/b747.h B747_ABI_VERSION
+ABI_VERSION = 15        # include/b747.h B747_ABI_VERSION
 
 NX, NDISC, NSIG, NAERO = 18, 9, 31, 5
 EVAL_ROWS = ("overshoot", "rise_time", "settling_time", "static_error", "itse", "length", "return")   # B747_NEVAL
@@ -88,6 +88,9 @@ SIGNATURES = {
     "b747_ppo_rollout": ([_PE, _PC, _PK, _V, _U64, _V, _I32] + [_V] * 6 + [_F32, _F32, _V], _I32),
     "b747_ppo_rollout_lanes": ([_PE, _PC, _PK, _V, _U64, _V, _I32] + [_V] * 6 + [_F32, _F32, _V], _I32),
     "b747_eval_episodes": ([_PE, _PC, _PK, _V, _I32, _I32, _F64, _V, _F64, _F32, _F32, _V, _V], _I32),
+    "b747_eval_population": ([_PE, _PC, _PK, _V, _I32, _I64, _I32, _V, _V, _I32, _I32, _F64, _V, _F64, _F32, _F32, _V, _V],
+                             _I32),
+    "b747_policy_pack_batch": ([_V, _I32, _I32, _I64, _V], _I32),
     "b747_ppo_update_workspace": ([_I32], _I64),
     "b747_ppo_grad": ([_V, _I32] + [_V] * 6 + [_I64, _F64, _F64, _F64, _V, _V, _V, _V], _I32),
     "b747_ppo_adam": ([_V, _V, _V, _V, _V, _I64] + [_F64] * 6 + [_V], _I32),

@@ -11,4 +11,10 @@ void launch_eval_episodes_faithful(const b747_env_batch &b, const b747_env_confi
     launch_eval_episodes<false>(b, cfg, C, ea, od, s);
 }
 
+void launch_eval_population_faithful(const b747_env_batch &b, const b747_env_config &cfg, const Consts &C,
+                                     const EvalArgs &ea, const PopArgs &pa, int od, hipStream_t s)
+{
+    launch_eval_population<false>(b, cfg, C, ea, pa, od, s);
+}
+
 }  // namespace b747

@@ -13,4 +13,10 @@ void launch_eval_episodes_fast(const b747_env_batch &b, const b747_env_config &c
     launch_eval_episodes<true>(b, cfg, C, ea, od, s);
 }
 
+void launch_eval_population_fast(const b747_env_batch &b, const b747_env_config &cfg, const Consts &C, const EvalArgs &ea,
+                                 const PopArgs &pa, int od, hipStream_t s)
+{
+    launch_eval_population<true>(b, cfg, C, ea, pa, od, s);
+}
+
 }  // namespace b747

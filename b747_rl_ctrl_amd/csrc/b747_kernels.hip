@@ -260,6 +260,63 @@ B747_API int32_t b747_eval_episodes(const b747_env_batch *b, const b747_env_conf
     return launched("b747_eval_episodes");
 }
 
+B747_API int32_t b747_policy_pack_batch(float *params, int32_t obs_dim, int32_t n_policies, int64_t policy_stride,
+                                        void *stream)
+{
+    if (!params) return bad_arg("b747_policy_pack_batch: params is NULL");
+    if (obs_dim < 1 || obs_dim > 10) return bad_arg("b747_policy_pack_batch: obs_dim");
+    if (n_policies < 0 || n_policies > 65535) return bad_arg("b747_policy_pack_batch: n_policies (0 .. 65535)");
+    if (policy_stride < policy_total_params(obs_dim) || policy_stride % 4 != 0)
+        return bad_arg("b747_policy_pack_batch: policy_stride (at least b747_policy_num_params floats, a multiple of 4)");
+    if (n_policies == 0) return 0;
+    hipLaunchKernelGGL(k_policy_pack_batch, dim3((policy_pack_threads(obs_dim) + 255) / 256, (unsigned)n_policies),
+                       dim3(256), 0, (hipStream_t)stream, params, (int)obs_dim, policy_stride);
+    return launched("b747_policy_pack_batch");
+}
+
+B747_API int32_t b747_eval_population(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c,
+                                      const float *params, int32_t n_policies, int64_t policy_stride,
+                                      int32_t envs_per_policy, const double *pid_ss, const double *pid_cs,
+                                      int32_t n_env_steps, int32_t sig_row, double scale, const double *y_base,
+                                      double error_band, float act_lo, float act_hi, double *eval_out, void *stream)
+{
+    int32_t r = check_env(b, cfg);
+    if (r <= 0) return r;
+    if (!c) return bad_arg("b747_eval_population: consts is NULL");
+    if (!y_base || !eval_out) return bad_arg("b747_eval_population: y_base / eval_out is NULL");
+    if (n_env_steps < 0) return bad_arg("b747_eval_population: n_env_steps < 0");
+    if (sig_row < 0 || sig_row >= B747_NSIG) return bad_arg("b747_eval_population: sig_row (a B747_SIG_* row)");
+    if (!(act_lo <= act_hi)) return bad_arg("b747_eval_population: act_lo > act_hi");
+    if (!b->x_f64) return bad_arg("b747_eval_population: x_f64 (the episode kernel keeps fp64 state only)");
+    if (cfg->auto_reset != 0)
+        return bad_arg("b747_eval_population: auto_reset must be 0 (an episode ends at its first done)");
+    if (params && b->obs_dim != 3 && b->obs_dim != 5)
+        return bad_arg("b747_eval_population: obs_dim (a policy runs with PID_LIKE 3 or SPEED_MODE 5 only; "
+                       "other observation types take params = NULL)");
+    if (!params && !b->action) return bad_arg("b747_eval_population: action is NULL (params = NULL holds b->action)");
+    if (params) {
+        if (envs_per_policy < 64 || envs_per_policy % 64 != 0)
+            return bad_arg("b747_eval_population: envs_per_policy (a positive multiple of 64: a wave flies one policy)");
+        if (n_policies < 1) return bad_arg("b747_eval_population: n_policies < 1 with params set");
+        if (b->n <= (int64_t)(n_policies - 1) * envs_per_policy || b->n > (int64_t)n_policies * envs_per_policy)
+            return bad_arg("b747_eval_population: n (outside ((n_policies - 1) * envs_per_policy, n_policies * "
+                           "envs_per_policy])");
+        if (policy_stride < policy_total_params(b->obs_dim) || policy_stride % 4 != 0)
+            return bad_arg("b747_eval_population: policy_stride (at least b747_policy_num_params floats and a multiple "
+                           "of 4: the fragments start on a 16-byte boundary)");
+    } else if (n_policies != 0) {
+        return bad_arg("b747_eval_population: n_policies must be 0 with params = NULL");
+    }
+    if (n_env_steps == 0) return 0;
+    const EvalArgs ea{params, n_env_steps, sig_row, scale, y_base, error_band, act_lo, act_hi, eval_out};
+    const PopArgs pa{policy_stride, params ? envs_per_policy / 64 : 1, pid_ss, pid_cs};
+    const Consts C = consts_of(c);
+    const int od = params ? b->obs_dim : 0;
+    if (b->variant != B747_VARIANT_FAITHFUL) launch_eval_population_fast(*b, *cfg, C, ea, pa, od, (hipStream_t)stream);
+    else launch_eval_population_faithful(*b, *cfg, C, ea, pa, od, (hipStream_t)stream);
+    return launched("b747_eval_population");
+}
+
 B747_API int64_t b747_ppo_update_workspace(int32_t obs_dim)
 {
     if (!policy_obs_dim_ok(obs_dim)) return bad_arg("obs_dim (3, 5, 7, 8 or 10)");

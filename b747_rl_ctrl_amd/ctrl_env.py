@@ -404,6 +404,49 @@ class BatchControllerEnv:
                    "b747_eval_episodes")
         return {k: out[j] for j, k in enumerate(_lib.EVAL_ROWS)}
 
+    def eval_population(self, n_env_steps: int, params: Optional[torch.Tensor] = None, envs_per_policy: int = 64,
+                        pid_ss=None, pid_cs=None, signal: str = "state_vartheta", scale: float = 1.0, y_base=None,
+                        error_band: float = 0.05, action=None, act_lo: float = None, act_hi: float = None, stream=None):
+        """eval_episodes with a policy per group of envs and PID gains per env, still ONE launch
+        (b747_eval_population, include/b747.h).  params [P, stride]: packed policies (evaluate.pack_policies); policy p
+        flies envs [p * envs_per_policy, (p + 1) * envs_per_policy) (a multiple of 64; the last group may be partial).
+        pid_ss / pid_cs [N, 4] (or [4] for every env; None = the batch's consts): env i's own SS / CS PID gains.  The
+        remaining arguments and the returned dict are eval_episodes'."""
+        from .model import SIG
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        b = self._batch()
+        with torch.cuda.stream(s):
+            yb = self.ref[0] * scale if y_base is None else \
+                torch.as_tensor(y_base, dtype=torch.float64, device=self.device).expand(self.n)
+            yb = yb.to(torch.float64).contiguous()
+            out = torch.empty(len(_lib.EVAL_ROWS), self.n, dtype=torch.float64, device=self.device)
+            gains = []
+            for g in (pid_ss, pid_cs):           # [N, 4] -> the kernel's [4][N]
+                if g is not None:
+                    g = torch.as_tensor(g, dtype=torch.float64).to(self.device)
+                    g = g.expand(self.n, 4).T.contiguous()
+                gains.append(g)
+            n_pol, stride = 0, 0
+            if params is None:
+                if action is None:
+                    self.action.zero_()
+                else:
+                    self.action.copy_(torch.as_tensor(action, dtype=torch.float32).to(self.device).expand(self.n))
+                b.action = self.action.data_ptr()
+            else:
+                assert params.dtype == torch.float32 and params.dim() == 2 and params.is_contiguous() \
+                    and params.device == self.device, \
+                    "params: [P, stride] packed fp32 policies (evaluate.pack_policies) on the env's device"
+                n_pol, stride = int(params.shape[0]), int(params.shape[1])
+        lo = float(self.action_space.low) if act_lo is None else float(act_lo)
+        hi = float(self.action_space.high) if act_hi is None else float(act_hi)
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        _lib.check(self._L.b747_eval_population(self._bref, self._cref, self._kref, ptr(params), n_pol, stride,
+                                                int(envs_per_policy), ptr(gains[0]), ptr(gains[1]), int(n_env_steps),
+                                                SIG[signal], float(scale), ptr(yb), float(error_band), lo, hi, ptr(out),
+                                                s.cuda_stream), "b747_eval_population")
+        return {k: out[j] for j, k in enumerate(_lib.EVAL_ROWS)}
+
     def step_seq(self, actions: torch.Tensor, stream=None):
         """len(actions) consecutive step() calls with actions [T, N] known in advance: T launches of the
         per-step kernel issued by one C call (b747_env_step_seq), so a host loop's per-call Python cost is

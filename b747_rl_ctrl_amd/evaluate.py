@@ -16,7 +16,9 @@ Semantics kept from calc_stepinfo(ys, y_base, error_band=0.05, ts):
   static_error   |ys[-1] - y_base|
 run_step_tests drives the env from Python, one recording launch per env step; run_step_tests_fused,
 monte_carlo_step_tests and PPO.step_tests fly the same episodes inside ONE kernel launch with the policy in the loop and
-the metrics accumulated in registers (b747_eval_episodes, include/b747.h).
+the metrics accumulated in registers (b747_eval_episodes, include/b747.h).  population_step_tests and
+pid_sweep_step_tests score many policies (one per 64-env wave) or many PID gain sets (one per env) in one such launch
+(b747_eval_population).
 (None in the reference -> NaN here; the reference raises ZeroDivisionError when y_base == ys[0],
 which gives NaN/inf ratios here.)
 """
@@ -182,6 +184,141 @@ def run_step_tests_fused(policy, vartheta_ref: Sequence[float],
     out = _fused_out(env, ev, vref, tk)
     out["env"] = env
     return out
+
+
+# ------------------------------------------------- populations: policies and PID gain sets in one launch --
+
+def pack_policies(policies, obs_dim: int, device) -> torch.Tensor:
+    """[P, stride] packed fp32 policies for BatchControllerEnv.eval_population, filled by ONE b747_policy_pack_batch
+    launch: row p is what packed_policy gives for policy p (stride = b747_policy_num_params, a multiple of 4).
+    policies: a sequence of ActorCritic / PPO, or a [P, n] tensor of ActorCritic.flat_params() rows."""
+    from . import _lib
+    L = _lib.lib()
+    stride = int(L.b747_policy_num_params(obs_dim))
+    _lib.check(min(stride, 0), "b747_policy_num_params")
+    if torch.is_tensor(policies):
+        rows = policies.detach()
+        assert rows.dim() == 2, "policies: [P, n] flat_params rows"
+    else:
+        flats = []
+        for p in policies:
+            net = p.policy if hasattr(p, "policy") and hasattr(p.policy, "flat_params") else p
+            flats.append(net.flat_params().detach())
+        rows = torch.stack(flats)
+    assert 1 <= rows.shape[1] <= stride, "policies: flat_params rows of this obs_dim"
+    buf = torch.zeros(rows.shape[0], stride, dtype=torch.float32, device=device)
+    buf[:, :rows.shape[1]].copy_(rows.to(device=device, dtype=torch.float32))
+    _lib.check(L.b747_policy_pack_batch(buf.data_ptr(), obs_dim, buf.shape[0], stride,
+                                        torch.cuda.current_stream(buf.device).cuda_stream), "b747_policy_pack_batch")
+    return buf
+
+
+def _population_out(env, ev, vref, tk, groups: int, group: int, keep: int) -> Dict[str, torch.Tensor]:
+    """_fused_out as [groups, keep] (the first `keep` envs of every `group`-env group; the last group may be
+    partial), the callback's means per group and the group with the best mean quality"""
+    flat = _fused_out(env, ev, vref, tk)
+    idx = (torch.arange(groups, device=env.device)[:, None] * group + torch.arange(keep, device=env.device)[None])
+    out = {k: v[idx] for k, v in flat.items() if torch.is_tensor(v) and v.dim() == 1}
+    out["mean_settling_time"] = out["settling_time"].mean(1)
+    out["mean_overshoot"] = out["overshoot"].mean(1)
+    out["mean_quality"] = out["quality"].mean(1)
+    out["best"] = out["mean_quality"].argmax()
+    return out
+
+
+def population_step_tests(policies, vartheta_ref: Sequence[float],
+                          state0: Sequence[float] = (0, 11000, 250, 0, 0, 0), tk: float = 60.0,
+                          observation_type: ObservationType = ObservationType.PID_LIKE,
+                          reward_type: RewardType = RewardType.CLASSIC,
+                          ctrl_mode: Optional[CtrlMode] = CtrlMode.DIRECT_CONTROL, norm_obs: bool = True,
+                          norm_act: bool = True, sample_time: Optional[float] = None, device="cuda",
+                          ctrl_type: CtrlType = CtrlType.MANUAL, **env_kwargs) -> Dict[str, torch.Tensor]:
+    """run_step_tests_fused for P policies in ONE launch: policy p flies the 64-env group p (the references repeated
+    to fill it; only its first len(vartheta_ref) envs are reported).  policies: what pack_policies takes.  Returns every metric of run_step_tests_fused as [P, R], the callback's
+    "mean_quality" / "mean_overshoot" / "mean_settling_time" as [P], and "best" (argmax of the mean quality)."""
+    R = len(vartheta_ref)
+    assert 1 <= R <= 64, "one 64-env group per policy"
+    dev = _lib_device(device)
+    obs_dim = {ObservationType.PID_LIKE: 3, ObservationType.SPEED_MODE: 5}[observation_type]
+    packed = pack_policies(policies, obs_dim, dev)
+    P = int(packed.shape[0])
+    n = (P - 1) * 64 + R                  # the last group needs its reported envs only
+    refs = torch.tensor((list(vartheta_ref) * 64)[:64] * P, dtype=torch.float64, device=dev)[:n]
+    env = BatchControllerEnv(n, observation_type, reward_type, norm_obs, norm_act, ctrl_type, ctrl_mode,
+                             reset_ref_mode=None, tk=tk, sample_time=sample_time, auto_reset=False,
+                             device=dev, **env_kwargs)
+    env.set_state0(torch.tensor(state0, dtype=torch.float64))
+    env.set_reference(vartheta=refs)
+    env.reset()
+    steps = int(math.ceil(tk / env.sample_time - 1e-9))
+    vref = env.ref[0].to(torch.float64)
+    ev = env.eval_population(steps, packed, 64, signal="state_vartheta", scale=180 / math.pi,
+                             y_base=vref * 180 / math.pi)
+    out = _population_out(env, ev, vref, tk, P, 64, R)
+    out["env"] = env
+    return out
+
+
+def pid_sweep_step_tests(gains, vartheta_ref: Sequence[float], loop: str = "SS", policy=None,
+                         state0: Sequence[float] = (0, 11000, 250, 0, 0, 0), tk: float = 60.0,
+                         observation_type: ObservationType = ObservationType.PID_LIKE,
+                         reward_type: RewardType = RewardType.CLASSIC, ctrl_mode: Optional[CtrlMode] = None,
+                         norm_obs: bool = True, norm_act: bool = True, sample_time: Optional[float] = None,
+                         device="cuda", **env_kwargs) -> Dict[str, torch.Tensor]:
+    """G sets of PID gains (gains [G, 4]) against R references in ONE launch of G * R envs: env g * R + r flies gain
+    set g against reference r.  loop "SS": the pitch-stabilisation PID's gains, vartheta_ref are pitch commands and
+    the pitch series is scored; "CS": the altitude-hold PID's gains, vartheta_ref are ALTITUDE commands and the
+    altitude series is scored against them (as agent_test.controller_test does).  policy None: the PID baseline
+    (AUTO for "SS", FULL_AUTO for "CS": agent_test.pid_baseline_env; sample_time defaults to dt).  With a policy
+    (loop "SS") ctrl_mode must be one of the ADD modes: the policy, one for every env, flies on top of the swept SS
+    PID.  Returns every metric as [G, R], the means as [G] and "best".  For "SS", "quality" is Controller.quality()
+    and best = argmax of its mean; for "CS" that formula needs the CS PID's last pitch command, which the kernel
+    does not return: "quality" is absent there and best = argmin of the mean ITSE it is built on."""
+    assert loop in ("SS", "CS")
+    dev = _lib_device(device)
+    g = torch.as_tensor(gains, dtype=torch.float64)
+    assert g.dim() == 2 and g.shape[1] == 4, "gains: [G, 4]"
+    G, R = int(g.shape[0]), len(vartheta_ref)
+    n = G * R
+    if policy is None:
+        ctrl_type = CtrlType.AUTO if loop == "SS" else CtrlType.FULL_AUTO
+    else:
+        assert loop == "SS" and ctrl_mode in (CtrlMode.ADD_DIRECT_CONTROL, CtrlMode.ADD_PROC_CONTROL), \
+            "a policy flies on top of the swept SS PID in the ADD control modes only"
+        ctrl_type = CtrlType.MANUAL
+    refs = torch.tensor(list(vartheta_ref) * G, dtype=torch.float64, device=dev)
+    env = BatchControllerEnv(n, observation_type, reward_type, norm_obs, norm_act, ctrl_type, ctrl_mode,
+                             reset_ref_mode=None, tk=tk, sample_time=sample_time, auto_reset=False,
+                             device=dev, **env_kwargs)
+    env.set_state0(torch.tensor(state0, dtype=torch.float64))
+    if loop == "SS":
+        env.set_reference(vartheta=refs)
+    else:
+        env.set_reference(h=refs)
+    env.reset()
+    steps = int(math.ceil(tk / env.sample_time - 1e-9))
+    per_env = g.to(dev).repeat_interleave(R, 0)               # [G * R, 4]
+    params, epp = None, 64
+    if policy is not None:                                      # one policy for the whole batch: one group
+        params = packed_policy(policy, env.obs_dim, env.device)[None]
+        epp = (n + 63) // 64 * 64
+    kw = dict(signal="state_vartheta", scale=180 / math.pi, y_base=refs * 180 / math.pi) if loop == "SS" else \
+        dict(signal="state_y", scale=1.0, y_base=refs)
+    ev = env.eval_population(steps, params, epp, pid_ss=per_env if loop == "SS" else None,
+                             pid_cs=per_env if loop == "CS" else None, **kw)
+    out = _population_out(env, ev, refs, tk, G, R, R)
+    out["itse"] = ev["itse"].reshape(G, R)
+    if loop == "CS":
+        for k in ("quality", "mean_quality"):
+            del out[k]
+        out["best"] = out["itse"].mean(1).argmin()
+    out["env"] = env
+    return out
+
+
+def _lib_device(device):
+    from . import _lib
+    return _lib.resolve_device(device)
 
 
 def monte_carlo_step_tests(policy, n: int, seed: int = 0, tk: float = 20.0,

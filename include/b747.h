@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define B747_ABI_VERSION 14  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
+#define B747_ABI_VERSION 15  /* 1: round 1; 2: + b747_set_specialization, b747_policy_*, b747_ppo_rollout;
                                 * 3: + b747_env_batch.rec_params, b747_struct_size; 4: + b747_env_batch.ep_stats;
                                 * 5: + b747_env_step_seq; 6: b747_model_batch.aero_err is double (the DLL's
                                 * `double aero_err[5]`, core/model.py:164), the policy buffer gains the layer-1
@@ -37,7 +37,8 @@ extern "C" {
                                 * b747_ppo_rollout advances *step_base by T on the device, b747_env_batch.ep_return is float
                                 * (it holds float32 values; 8 B less per env step); 11: + b747_eval_episodes;
                                 * 12: + b747_ppo_update_workspace, b747_ppo_grad, b747_ppo_adam; 13: + b747_ppo_gae,
-                                * b747_ppo_epoch, b747_get_specialization; 14: + b747_ppo_rollout_lanes */
+                                * b747_ppo_epoch, b747_get_specialization; 14: + b747_ppo_rollout_lanes; 15: + b747_eval_population,
+                                * b747_policy_pack_batch */
 
 #define B747_NX 18   /* continuous states, SURVEY A.1 (dll.data@0x2b380) */
 #define B747_NDISC 9 /* compact discrete state, see b747_model_batch.disc */
@@ -369,6 +370,34 @@ int32_t b747_eval_episodes(const b747_env_batch *b, const b747_env_config *cfg, 
                            int32_t n_env_steps, int32_t sig_row, double scale, const double *y_base /* [N] */,
                            double error_band, float act_lo, float act_hi,
                            double *eval_out /* [B747_NEVAL][N] */, void *stream);
+
+/* ---- a population of policies and PID gain sets scored in one launch (ABI 15) ----
+ * b747_eval_episodes with a policy per group of envs and PID gains per env; everything not named here -- the episode
+ * semantics and frozen envs, eval_out, what is left in the batch, the configurations covered -- is as above.
+ * params [n_policies][policy_stride] floats: policy p (packed by b747_policy_pack or b747_policy_pack_batch) starts at
+ * params + p * policy_stride and flies envs [p * envs_per_policy, (p + 1) * envs_per_policy); the last group may be
+ * partial.  envs_per_policy is a positive multiple of 64: each 64-env wave reads one policy, at a wave-uniform address.
+ * params == NULL (n_policies 0): no policy, b->action held, as above.  pid_ss / pid_cs (each nullable, [4][N] double,
+ * component-major as every batch field): env i flies with PID_SS[j] = pid_ss[j * N + i] (PID_CS likewise) in place of
+ * c->PID_SS; a NULL pointer keeps the batch constant.  The gains enter the control law only; resets do not read them.
+ * With n_policies == 1 and both gain pointers NULL the result is b747_eval_episodes' bit for bit.  Returns
+ * -hipErrorInvalidValue, with the field named in b747_last_error and before any launch, for everything
+ * b747_eval_episodes refuses and, with params set, for envs_per_policy not a positive multiple of 64, n_policies < 1,
+ * N outside ((n_policies - 1) * envs_per_policy, n_policies * envs_per_policy], policy_stride below
+ * b747_policy_num_params(obs_dim) or not a multiple of 4 (the matrix-core fragments start on a 16-byte boundary);
+ * with params == NULL for n_policies != 0.  n_env_steps == 0 validates and launches nothing.  Stream-ordered,
+ * graph-capturable, no allocation. */
+int32_t b747_eval_population(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c,
+                             const float *params /* [n_policies][policy_stride], NULL = no policy */,
+                             int32_t n_policies, int64_t policy_stride /* floats */, int32_t envs_per_policy,
+                             const double *pid_ss /* [4][N], NULL = c->PID_SS */,
+                             const double *pid_cs /* [4][N], NULL = c->PID_CS */,
+                             int32_t n_env_steps, int32_t sig_row, double scale, const double *y_base, double error_band,
+                             float act_lo, float act_hi, double *eval_out /* [B747_NEVAL][N] */, void *stream);
+/* b747_policy_pack for n_policies parameter sets in ONE launch: set p occupies params + p * policy_stride (its flat
+ * parameters first, as for b747_policy_pack; policy_stride >= b747_policy_num_params(obs_dim), a multiple of 4, at most
+ * 65535 sets).  Floats of a stride past b747_policy_num_params are not touched. */
+int32_t b747_policy_pack_batch(float *params, int32_t obs_dim, int32_t n_policies, int64_t policy_stride, void *stream);
 
 /* ---- one PPO minibatch update on the device (b747_rl_ctrl_amd/ppo.py PPO._minibatch; SB3 1.4 PPO.train) ----
  * For the policy of b747_policy_act (pi / vf nets obs_dim -> 64 -> 64 tanh, action_net, value_net, log_std; obs_dim 3, 5,
