@@ -96,6 +96,11 @@ SIGNATURES = {
     "b747_ppo_adam": ([_V, _V, _V, _V, _V, _I64] + [_F64] * 6 + [_V], _I32),
     "b747_ppo_epoch": ([_V, _I32] + [_V] * 6 + [_I64, _I64, _F64, _F64, _F64] + [_V] * 5 + [_F64] * 5 + [_V, _V], _I32),
     "b747_ppo_gae": ([_V, _V, _V, _V, _I32, _I64, _F64, _F64, _V, _V, _V], _I32),
+    # (additive under ABI 15: a library built before them reports 15 and is caught by bind()'s missing-entry-point check)
+    "b747_ppo_rollout_population": ([_PE, _PC, _PK, _V, _I32, _I64, _I32, _V, _U64, _V, _I32] + [_V] * 7
+                                    + [_F32, _F32, _V], _I32),
+    "b747_ppo_epoch_population": ([_V, _I32, _I64, _I32] + [_V] * 6 + [_I64, _I64, _F64, _F64, _F64] + [_V] * 5
+                                  + [_F64, ctypes.POINTER(_F64), _F64, _F64, _F64, _V, _V], _I32),
 }
 
 

@@ -317,6 +317,53 @@ B747_API int32_t b747_eval_population(const b747_env_batch *b, const b747_env_co
     return launched("b747_eval_population");
 }
 
+B747_API int32_t b747_ppo_rollout_population(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c,
+                                             const float *params, int32_t n_policies, int64_t policy_stride,
+                                             int32_t envs_per_policy, const double *rew_pop, uint64_t seed,
+                                             uint64_t *step_base, int32_t T, float *obs_buf, float *act_buf,
+                                             float *logp_buf, float *val_buf, float *rew_buf, uint8_t *done_buf,
+                                             float *last_val, float act_lo, float act_hi, void *stream)
+{
+    int32_t r = check_env(b, cfg);
+    if (r < 0) return r;
+    if (!c) return bad_arg("b747_ppo_rollout_population: consts is NULL");
+    if (!params) return bad_arg("b747_ppo_rollout_population: params is NULL");
+    if (!obs_buf) return bad_arg("b747_ppo_rollout_population: obs_buf is NULL");
+    if (!act_buf) return bad_arg("b747_ppo_rollout_population: act_buf is NULL");
+    if (!logp_buf) return bad_arg("b747_ppo_rollout_population: logp_buf is NULL");
+    if (!val_buf) return bad_arg("b747_ppo_rollout_population: val_buf is NULL");
+    if (!rew_buf) return bad_arg("b747_ppo_rollout_population: rew_buf is NULL");
+    if (!done_buf) return bad_arg("b747_ppo_rollout_population: done_buf is NULL");
+    if (T < 0) return bad_arg("b747_ppo_rollout_population: T < 0");
+    if (!(act_lo <= act_hi)) return bad_arg("b747_ppo_rollout_population: act_lo > act_hi");
+    if (envs_per_policy < 64 || envs_per_policy % 64 != 0)
+        return bad_arg("b747_ppo_rollout_population: envs_per_policy (a positive multiple of 64: a wave flies one policy)");
+    if (n_policies < 1) return bad_arg("b747_ppo_rollout_population: n_policies < 1");
+    if (r == 0) return bad_arg("b747_ppo_rollout_population: n (an empty batch holds no group)");
+    if (b->obs_dim != 3 && b->obs_dim != 5)
+        return bad_arg("b747_ppo_rollout_population: obs_dim (the one-wave rollout kernel runs a policy with PID_LIKE 3 or "
+                       "SPEED_MODE 5 only)");
+    if (!b->x_f64) return bad_arg("b747_ppo_rollout_population: x_f64 (the one-wave rollout kernel keeps fp64 state only)");
+    if (b->sig)
+        return bad_arg("b747_ppo_rollout_population: sig (no per-DLL-step signal recording inside the rollout kernel)");
+    if (b->n <= (int64_t)(n_policies - 1) * envs_per_policy || b->n > (int64_t)n_policies * envs_per_policy)
+        return bad_arg("b747_ppo_rollout_population: n (outside ((n_policies - 1) * envs_per_policy, n_policies * "
+                       "envs_per_policy])");
+    if (policy_stride < policy_total_params(b->obs_dim) || policy_stride % 4 != 0)
+        return bad_arg("b747_ppo_rollout_population: policy_stride (at least b747_policy_num_params floats and a multiple "
+                       "of 4: the fragments start on a 16-byte boundary)");
+    if (T == 0) return 0;
+    const RolloutLanesArgs ra{params, seed, step_base, T, act_lo, act_hi, obs_buf, act_buf, logp_buf, val_buf, rew_buf,
+                              done_buf};
+    const RolloutPopArgs pa{policy_stride, envs_per_policy / 64, rew_pop, last_val};
+    const Consts C = consts_of(c);
+    // (the launcher's second launch advances *step_base by T: ordered after the rollout kernel's last read of it)
+    if (b->variant != B747_VARIANT_FAITHFUL)
+        launch_rollout_population_fast(*b, *cfg, C, ra, pa, b->obs_dim, step_base, (hipStream_t)stream);
+    else launch_rollout_population_faithful(*b, *cfg, C, ra, pa, b->obs_dim, step_base, (hipStream_t)stream);
+    return launched("b747_ppo_rollout_population");
+}
+
 B747_API int64_t b747_ppo_update_workspace(int32_t obs_dim)
 {
     if (!policy_obs_dim_ok(obs_dim)) return bad_arg("obs_dim (3, 5, 7, 8 or 10)");
@@ -404,6 +451,54 @@ B747_API int32_t b747_ppo_epoch(float *theta, int32_t obs_dim, const float *obs,
                     launch_ppo_epoch(theta, obs_dim, obs, act, old_logp, adv, ret, perm, n_rows, batch_size, clip_range,
                                      ent_coef, vf_coef, workspace, grad, m, v, t, max_grad_norm, lr, beta1, beta2, eps,
                                      stats, (hipStream_t)stream));
+}
+
+B747_API int32_t b747_ppo_epoch_population(float *theta, int32_t n_policies, int64_t policy_stride, int32_t obs_dim,
+                                           const float *obs, const float *act, const float *old_logp, const float *adv,
+                                           const float *ret, const int64_t *perm, int64_t n_rows, int64_t batch_size,
+                                           double clip_range, double ent_coef, double vf_coef, void *workspace,
+                                           float *grad, float *m, float *v, int64_t *t, double max_grad_norm,
+                                           const double *lr, double beta1, double beta2, double eps, float *stats,
+                                           void *stream)
+{
+    if (!theta) return bad_arg("b747_ppo_epoch_population: theta is NULL");
+    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("b747_ppo_epoch_population: obs_dim (3, 5, 7, 8 or 10)");
+    if (n_policies < 1) return bad_arg("b747_ppo_epoch_population: n_policies < 1");
+    if (policy_stride < policy_total_params(obs_dim) || policy_stride % 4 != 0)
+        return bad_arg("b747_ppo_epoch_population: policy_stride (at least b747_policy_num_params floats and a multiple "
+                       "of 4)");
+    if (!obs) return bad_arg("b747_ppo_epoch_population: obs is NULL");
+    if (!act) return bad_arg("b747_ppo_epoch_population: act is NULL");
+    if (!old_logp) return bad_arg("b747_ppo_epoch_population: old_logp is NULL");
+    if (!adv) return bad_arg("b747_ppo_epoch_population: adv is NULL");
+    if (!ret) return bad_arg("b747_ppo_epoch_population: ret is NULL");
+    if (!perm) return bad_arg("b747_ppo_epoch_population: perm is NULL");
+    if (n_rows < 2)
+        return bad_arg("b747_ppo_epoch_population: n_rows < 2 (the advantages' standard deviation needs two rows)");
+    if (batch_size < 2)
+        return bad_arg("b747_ppo_epoch_population: batch_size < 2 (the advantages' standard deviation needs two rows)");
+    if (n_rows % batch_size == 1)
+        return bad_arg("b747_ppo_epoch_population: n_rows % batch_size == 1 (the last minibatch would be one row: no "
+                       "standard deviation)");
+    if (!workspace) return bad_arg("b747_ppo_epoch_population: workspace is NULL");
+    if (!grad) return bad_arg("b747_ppo_epoch_population: grad is NULL");
+    if (!m) return bad_arg("b747_ppo_epoch_population: m is NULL");
+    if (!v) return bad_arg("b747_ppo_epoch_population: v is NULL");
+    if (!t) return bad_arg("b747_ppo_epoch_population: t is NULL");
+    if (!lr) return bad_arg("b747_ppo_epoch_population: lr is NULL (a host array, one learning rate per member)");
+    if (!stats) return bad_arg("b747_ppo_epoch_population: stats is NULL");
+    // member p: b747_ppo_epoch's launches on its own parameters, moments, step count, sample order and statistics
+    // rows; the rollout buffers, the gradient and the workspace are shared (the stream orders the members)
+    const int64_t n_params = PolicyLayout::of(obs_dim).total, n_mb = (n_rows + batch_size - 1) / batch_size;
+    for (int32_t p = 0; p < n_policies; ++p) {
+        const hipError_t e = launch_ppo_epoch(theta + p * policy_stride, obs_dim, obs, act, old_logp, adv, ret,
+                                              perm + p * n_rows, n_rows, batch_size, clip_range, ent_coef, vf_coef,
+                                              workspace, grad, m + p * n_params, v + p * n_params, t + p, max_grad_norm,
+                                              lr[p], beta1, beta2, eps, stats + p * n_mb * kUpdStats,
+                                              (hipStream_t)stream);
+        if (e != hipSuccess) return fail(e, "b747_ppo_epoch_population");
+    }
+    return 0;
 }
 
 B747_API int32_t b747_consts_default(b747_consts *c)

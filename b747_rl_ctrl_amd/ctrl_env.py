@@ -240,7 +240,19 @@ class BatchControllerEnv:
 
     def set_rew_config(self, rew_config: dict):
         """env/ctrl_env.py:250-252 -- reward constants (reward_config keys of :109-192)."""
-        c = self.cfg
+        for j, v in enumerate(self._rew_values(rew_config)):
+            self.cfg.rew[j] = float(v)
+
+    def rew_constants(self, rew_config: Optional[dict] = None) -> list:
+        """The eight doubles of cfg.rew (include/b747.h b747_env_config.rew) that set_rew_config(rew_config) would
+        leave in this env's configuration, without changing it: one row of ppo_rollout_population's rew_pop."""
+        out = [float(self.cfg.rew[j]) for j in range(8)]
+        for j, v in enumerate(self._rew_values(rew_config or {})):
+            out[j] = float(v)
+        return out
+
+    def _rew_values(self, rew_config: dict) -> list:
+        """set_rew_config's table: the leading cfg.rew entries a reward_config sets for this reward type"""
         if self.reward_type == RewardType.CLASSIC:
             k1, k2, k3 = rew_config.get("k1", 2), rew_config.get("k2", 2), rew_config.get("k3", 1)
             s = k1 + k2 + k3
@@ -254,8 +266,7 @@ class BatchControllerEnv:
             vals = [rew_config.get("overshoot_ref", 2), rew_config.get("tp_ref", 5), rew_config.get("k", 0.1)]
         else:
             vals = []
-        for j, v in enumerate(vals):
-            c.rew[j] = float(v)
+        return vals
 
     def set_state0(self, state0):
         """Per-env (or shared) initial state used by resets when reset_ref_mode is None."""
@@ -446,6 +457,42 @@ class BatchControllerEnv:
                                                 SIG[signal], float(scale), ptr(yb), float(error_band), lo, hi, ptr(out),
                                                 s.cuda_stream), "b747_eval_population")
         return {k: out[j] for j, k in enumerate(_lib.EVAL_ROWS)}
+
+    def ppo_rollout_population(self, T: int, params: torch.Tensor, obs_buf, act_buf, logp_buf, val_buf, rew_buf,
+                               done_buf, seed: int = 0, step_base: Optional[torch.Tensor] = None,
+                               envs_per_policy: int = 64, rew_pop: Optional[torch.Tensor] = None,
+                               last_val: Optional[torch.Tensor] = None, act_lo: float = None, act_hi: float = None,
+                               stream=None, check: bool = True) -> int:
+        """T stochastic rollout steps for P learners side by side in ONE launch (b747_ppo_rollout_population,
+        include/b747.h).  params [P, stride]: packed policies (evaluate.pack_policies); policy p flies envs
+        [p * envs_per_policy, (p + 1) * envs_per_policy) (a multiple of 64; the last group may be partial).  rew_pop
+        [P, 8] float64 (None = the env's own reward constants for everyone): group p's reward constants, rows of
+        rew_constants().  The six rollout buffers are time-major ([T, N, ...], row t * N + i); step_base: one device
+        int64, the Philox counter base, advanced by T on the device; last_val [N] float32 (optional) receives the
+        value of the observation the rollout ends on.  Returns the library's code (raises on failure unless
+        check=False)."""
+        s = torch.cuda.current_stream(self.device) if stream is None else stream
+        b = self._batch()
+        b.action = self.action.data_ptr()       # the kernel leaves the last clipped action there
+        assert params.dtype == torch.float32 and params.dim() == 2 and params.is_contiguous() \
+            and params.device == self.device, \
+            "params: [P, stride] packed fp32 policies (evaluate.pack_policies) on the env's device"
+        if rew_pop is not None:
+            assert rew_pop.dtype == torch.float64 and rew_pop.is_contiguous() and rew_pop.device == self.device \
+                and tuple(rew_pop.shape) == (params.shape[0], 8), "rew_pop: [P, 8] float64 on the env's device"
+        if last_val is not None:
+            assert last_val.dtype == torch.float32 and last_val.is_contiguous() and last_val.numel() == self.n \
+                and last_val.device == self.device, "last_val: [N] float32 on the env's device"
+        lo = float(self.action_space.low) if act_lo is None else float(act_lo)
+        hi = float(self.action_space.high) if act_hi is None else float(act_hi)
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        rc = self._L.b747_ppo_rollout_population(
+            self._bref, self._cref, self._kref, ptr(params), int(params.shape[0]), int(params.shape[1]),
+            int(envs_per_policy), ptr(rew_pop), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step_base), int(T), ptr(obs_buf),
+            ptr(act_buf), ptr(logp_buf), ptr(val_buf), ptr(rew_buf), ptr(done_buf), ptr(last_val), lo, hi, s.cuda_stream)
+        if check:
+            _lib.check(rc, "b747_ppo_rollout_population")
+        return int(rc)
 
     def step_seq(self, actions: torch.Tensor, stream=None):
         """len(actions) consecutive step() calls with actions [T, N] known in advance: T launches of the

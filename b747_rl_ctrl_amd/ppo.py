@@ -18,6 +18,7 @@ shard (global env ids rank*N + i, so the Philox streams never overlap) and colle
 ONE all-reduce of the flat gradient bucket (~9k fp32, 36 KB) per minibatch before clipping and the
 Adam step -- the only collective, once per minibatch, never on the rollout path.
 """
+import ctypes
 import math
 from dataclasses import dataclass
 from typing import Callable, Optional, Union
@@ -566,3 +567,180 @@ class PPO:
                   variant={0: "fast", 1: "faithful", 2: "mixed"}[e.variant])
         kw.update(kwargs)
         return run_step_tests_fused(policy, vartheta_ref, state0=state0, tk=e.tk if tk is None else tk, **kw)
+
+
+class PopulationPPO:
+    """P independent PPO learners on ONE BatchControllerEnv, their rollouts flown side by side in one launch
+    (b747_ppo_rollout_population, include/b747.h).
+
+    Member p owns envs [p * envs_per_member, (p + 1) * envs_per_member) of `env`, its own policy (ActorCritic(obs_dim)
+    built after torch.manual_seed(seeds[p]): what PPO(seed=seeds[p]) builds), its own reward constants
+    (rew_configs[p], a reward_config dict as BatchControllerEnv.set_rew_config takes; None = the env's) and its own
+    learning rate; gamma, gae_lambda, the clip range, the epochs and the batch size (rows of ONE member per minibatch) are
+    cfg's, shared.  This is the shape of the reference's ControllerAgent.optimize() (neural/agent.py:89-136): trials
+    that differ in reward_config and hyper-parameters, ranked by ControlTestCallback.mean_quality -- step_tests()
+    here.  The update is PPO(fused_update=True, epoch_call=True)'s, per member, from one C call per epoch
+    (b747_ppo_epoch_population): the same kernels, the same bits as P separate learners
+    (tests/test_gpu_ppo_population_train.py).  `seed` keys the action noise (Philox counters (seed, step, global env
+    id), shared by the members, whose env ids differ).  No torch modules are kept: `flat` [P, stride] is the master copy
+    of every member's parameters (member(p) gives an ActorCritic copy)."""
+
+    def __init__(self, env: BatchControllerEnv, n_members: int, envs_per_member: int = 64,
+                 cfg: Optional[PPOConfig] = None, seeds=None, rew_configs=None, learning_rates=None, seed: int = 0):
+        from . import _lib
+        from .evaluate import pack_policies
+        self._lib, self._L = _lib, _lib.lib()
+        self.env, self.cfg, self.seed = env, cfg or PPOConfig(), int(seed)
+        P, epp, n, od, dev = int(n_members), int(envs_per_member), env.n, env.obs_dim, env.device
+        self.n_members, self.envs_per_member = P, epp
+        if P < 1 or epp < 64 or epp % 64 != 0 or not ((P - 1) * epp < n <= P * epp):
+            raise ValueError(f"PopulationPPO: {P} members of {epp} envs (a positive multiple of 64) do not tile the "
+                             f"env's {n} envs (the last member may be partial)")
+        self.seeds = [self.seed + p for p in range(P)] if seeds is None else [int(s) for s in seeds]
+        lrs = [self.cfg.learning_rate] * P if learning_rates is None else [float(x) for x in learning_rates]
+        if len(self.seeds) != P or len(lrs) != P or (rew_configs is not None and len(rew_configs) != P):
+            raise ValueError("PopulationPPO: seeds, rew_configs and learning_rates take one entry per member")
+        self.learning_rates = lrs
+        self._lr = (ctypes.c_double * P)(*lrs)            # b747_ppo_epoch_population reads them on the host
+        nets = []
+        for s in self.seeds:
+            torch.manual_seed(s)
+            nets.append(ActorCritic(od))
+        self.n_params = sum(p.numel() for p in nets[0].flat_param_list())
+        self.flat = pack_policies(nets, od, dev)          # [P, stride], one b747_policy_pack_batch launch
+        self.stride = int(self.flat.shape[1])
+        rows = [env.rew_constants(None if rew_configs is None else rew_configs[p]) for p in range(P)]
+        self.rew = torch.tensor(rows, dtype=torch.float64, device=dev)
+        self._rew_arg = None if rew_configs is None else self.rew     # (None: the kernel without the per-group loads)
+        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)
+        T = self.cfg.n_steps
+        self.upd_m, self.upd_v, self.upd_grad = z(P, self.n_params), z(P, self.n_params), z(self.n_params)
+        self.upd_t = torch.zeros(P, dtype=torch.int64, device=dev)
+        ws = int(self._L.b747_ppo_update_workspace(od))
+        if ws <= 0:
+            raise ValueError(f"PopulationPPO does not cover this policy: {self._L.b747_last_error().decode()}")
+        self.upd_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
+        self.obs_buf, self.act_buf = z(T, n, od), z(T, n, 1)
+        self.logp_buf, self.val_buf, self.rew_buf = z(T, n), z(T, n), z(T, n)
+        self.done_buf = z(T, n, dt=torch.bool)
+        self.adv_buf, self.ret_buf = z(T, n), z(T, n)
+        self.last_val = z(n)
+        self.step_base = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.act_lo, self.act_hi = float(env.action_space.low), float(env.action_space.high)
+        if self._rollout(0) != 0:                         # T = 0: validates the configuration, launches nothing
+            raise ValueError(f"b747_ppo_rollout_population does not cover this env: {self._L.b747_last_error().decode()}")
+
+    def _rollout(self, T: int) -> int:
+        return self.env.ppo_rollout_population(
+            T, self.flat, self.obs_buf, self.act_buf, self.logp_buf, self.val_buf, self.rew_buf, self.done_buf,
+            seed=self.seed, step_base=self.step_base, envs_per_policy=self.envs_per_member, rew_pop=self._rew_arg,
+            last_val=self.last_val, act_lo=self.act_lo, act_hi=self.act_hi, check=False)
+
+    @torch.no_grad()
+    def collect_rollouts(self, n_steps: Optional[int] = None):
+        """n_steps (default cfg.n_steps) policy + env steps of every member: one b747_ppo_rollout_population call.  It
+        also leaves the bootstrap values in last_val and advances step_base."""
+        T = n_steps or self.cfg.n_steps
+        assert T <= self.cfg.n_steps
+        self._lib.check(self._rollout(T), "b747_ppo_rollout_population")
+        return T
+
+    @torch.no_grad()
+    def compute_gae(self, T: Optional[int] = None):
+        """PPO.compute_gae for every member: one b747_ppo_gae launch over all N envs, bootstrapped with the rollout
+        kernel's last_val"""
+        T, c, p = T or self.cfg.n_steps, self.cfg, lambda x: x.data_ptr()
+        self._lib.check(self._L.b747_ppo_gae(
+            p(self.rew_buf), p(self.val_buf), p(self.done_buf), p(self.last_val), T, self.env.n, c.gamma, c.gae_lambda,
+            p(self.adv_buf), p(self.ret_buf), torch.cuda.current_stream().cuda_stream), "b747_ppo_gae")
+
+    def member_rows(self, T: int) -> torch.Tensor:
+        """[P, T * envs_per_member] the rollout rows t * N + p * envs_per_member + j of each member, in the order
+        (t, j) of a learner that had the member's envs to itself"""
+        P, epp, dev = self.n_members, self.envs_per_member, self.env.device
+        t = torch.arange(T, device=dev)[None, :, None] * self.env.n
+        return (t + torch.arange(P, device=dev)[:, None, None] * epp + torch.arange(epp, device=dev)[None, None]) \
+            .reshape(P, T * epp)
+
+    @torch.no_grad()
+    def train(self, T: Optional[int] = None,
+              minibatch_order: Optional[Callable[[int, int, int, int], torch.Tensor]] = None):
+        """PPO.train(fused_update, epoch_call) for every member: per epoch one sample order per member and ONE
+        b747_ppo_epoch_population call; afterwards one b747_policy_pack_batch.
+        minibatch_order(epoch, T, envs_per_member, p) -> [T * envs_per_member] indices into MEMBER p's own time-major
+        rows (t * envs_per_member + j: what PPO.train's hook gives a learner that has the member's envs to itself);
+        default torch.randperm.  Returns PPO.train's names as [P] tensors (float64; explained_variance and std
+        float32-derived), per member."""
+        T, c, P, epp = T or self.cfg.n_steps, self.cfg, self.n_members, self.envs_per_member
+        if self.env.n != P * epp:
+            raise ValueError("PopulationPPO.train: every member needs envs_per_member envs (one n_rows for all members)")
+        dev, n_rows, p = self.env.device, T * epp, lambda x: x.data_ptr()
+        n_mb = -(-n_rows // c.batch_size)
+        rows_of = self.member_rows(T)
+        stats = torch.empty(c.n_epochs, P, n_mb, 8, dtype=torch.float32, device=dev)
+        for epoch in range(c.n_epochs):
+            if minibatch_order is None:
+                local = torch.stack([torch.randperm(n_rows, device=dev) for _ in range(P)])
+            else:
+                local = torch.stack([torch.as_tensor(minibatch_order(epoch, T, epp, m), device=dev).to(torch.int64)
+                                     for m in range(P)])
+            assert tuple(local.shape) == (P, n_rows), "minibatch_order must give every row of the member once"
+            perm = torch.gather(rows_of, 1, local).contiguous()       # member rows -> rows t * N + i of the buffers
+            self._lib.check(self._L.b747_ppo_epoch_population(
+                p(self.flat), P, self.stride, self.env.obs_dim, p(self.obs_buf), p(self.act_buf), p(self.logp_buf),
+                p(self.adv_buf), p(self.ret_buf), p(perm), n_rows, c.batch_size, c.clip_range, c.ent_coef, c.vf_coef,
+                p(self.upd_ws), p(self.upd_grad), p(self.upd_m), p(self.upd_v), p(self.upd_t), c.max_grad_norm, self._lr,
+                0.9, 0.999, 1e-5, p(stats[epoch]), torch.cuda.current_stream().cuda_stream), "b747_ppo_epoch_population")
+        self.repack()
+        st = stats.double()
+        mean, last = st.mean(dim=(0, 2)), st[-1].mean(dim=1)          # [P, 8]: every minibatch / the last epoch's
+        v = self.val_buf[:T].reshape(T, P, epp).permute(1, 0, 2).reshape(P, -1)
+        r = self.ret_buf[:T].reshape(T, P, epp).permute(1, 0, 2).reshape(P, -1)
+        var_r = r.var(dim=1, unbiased=False)
+        ev = torch.where(var_r != 0, 1 - (r - v).var(dim=1, unbiased=False) / var_r, torch.full_like(var_r, float("nan")))
+        out = {"entropy_loss": mean[:, 2], "policy_gradient_loss": mean[:, 0], "value_loss": mean[:, 1],
+               "approx_kl": last[:, 4], "clip_fraction": mean[:, 3], "loss": st[-1, :, -1, 7],
+               "explained_variance": ev, "std": self.flat[:, self.n_params - 1].exp(),
+               "pg_term_scale": mean[:, 5], "kl_term_scale": last[:, 6]}
+        out["policy_loss"] = out["policy_gradient_loss"]
+        return out
+
+    def repack(self):
+        """Derive the packed sections of every member from its flat parameters (after an update): one launch"""
+        self._lib.check(self._L.b747_policy_pack_batch(self.flat.data_ptr(), self.env.obs_dim, self.n_members, self.stride,
+                                                       torch.cuda.current_stream().cuda_stream), "b747_policy_pack_batch")
+
+    def learn(self, iterations: int, n_steps: Optional[int] = None, minibatch_order=None):
+        T, P, epp = n_steps or self.cfg.n_steps, self.n_members, self.envs_per_member
+        self.env.reset()
+        hist = []
+        for _ in range(iterations):
+            self.collect_rollouts(T)
+            self.compute_gae(T)
+            st = self.train(T, minibatch_order)
+            st["mean_reward"] = self.rew_buf[:T].reshape(T, P, epp).mean(dim=(0, 2))
+            hist.append(st)
+        return hist
+
+    def member(self, p: int) -> ActorCritic:
+        """A copy of member p's policy as an ActorCritic on the env's device"""
+        net = ActorCritic(self.env.obs_dim).to(self.env.device)
+        with torch.no_grad():
+            off = 0
+            for prm in net.flat_param_list():
+                prm.copy_(self.flat[p, off:off + prm.numel()].view_as(prm))
+                off += prm.numel()
+        return net
+
+    def step_tests(self, vartheta_ref, state0=(0, 11000, 250, 0, 0, 0), tk: Optional[float] = None, **kwargs):
+        """PPO.step_tests for every member in ONE launch (evaluate.population_step_tests on the packed buffer): the
+        reference's ControlTestCallback metrics as [P, R], its means "mean_quality" / "mean_overshoot" /
+        "mean_settling_time" as [P] and "best", the member optimize() would keep."""
+        from .evaluate import population_step_tests
+        e = self.env
+        kw = dict(observation_type=e.observation_type, reward_type=e.reward_type, ctrl_mode=e.ctrl_mode,
+                  norm_obs=e.norm_obs, norm_act=e.norm_act, sample_time=e.sample_time, device=e.device,
+                  action_max=e.action_max, vartheta_max=e.vartheta_max, use_limiter=e.use_limiter,
+                  variant={0: "fast", 1: "faithful", 2: "mixed"}[e.variant])
+        kw.update(kwargs)
+        return population_step_tests(self.flat, vartheta_ref, state0=state0, tk=e.tk if tk is None else tk, **kw)

@@ -38,7 +38,10 @@ extern "C" {
                                 * (it holds float32 values; 8 B less per env step); 11: + b747_eval_episodes;
                                 * 12: + b747_ppo_update_workspace, b747_ppo_grad, b747_ppo_adam; 13: + b747_ppo_gae,
                                 * b747_ppo_epoch, b747_get_specialization; 14: + b747_ppo_rollout_lanes; 15: + b747_eval_population,
-                                * b747_policy_pack_batch */
+                                * b747_policy_pack_batch.  b747_ppo_rollout_population and b747_ppo_epoch_population
+                                * came later as purely additive entry points under 15 (no struct, argument or
+                                * behaviour of an existing one changed): a library built before them still reports
+                                * 15, and a binding catches it by the missing entry point (_lib.bind) */
 
 #define B747_NX 18   /* continuous states, SURVEY A.1 (dll.data@0x2b380) */
 #define B747_NDISC 9 /* compact discrete state, see b747_model_batch.disc */
@@ -336,6 +339,31 @@ int32_t b747_ppo_rollout_lanes(const b747_env_batch *b, const b747_env_config *c
                                const float *params, uint64_t seed, uint64_t *step_base, int32_t T, float *obs_buf,
                                float *act_buf, float *logp_buf, float *val_buf, float *rew_buf, uint8_t *done_buf,
                                float act_lo, float act_hi, void *stream);
+/* P learners' rollouts side by side in ONE launch (additive under ABI 15): b747_ppo_rollout_lanes with a policy and
+ * reward constants per group of envs; everything not named here -- the rows, the Philox counters (seed, env_offset + i,
+ * *step_base + t), the episode books and auto-reset, what is left in the env, the configurations covered -- is as
+ * above.  params [n_policies][policy_stride] floats: policy p (packed by b747_policy_pack or b747_policy_pack_batch)
+ * starts at params + p * policy_stride and flies envs [p * envs_per_policy, (p + 1) * envs_per_policy); the last group
+ * may be partial.  envs_per_policy is a positive multiple of 64: each 64-env wave reads one policy, at a wave-uniform
+ * address.  rew_pop (nullable, [n_policies][8] double in cfg->rew order): group p's envs are rewarded with rew_pop[p]
+ * in place of cfg->rew; only the reward reads them, resets do not.  The value head runs in the step loop for both
+ * obs_dims (the batched value pass takes one policy for all rows), and a one-thread launch then advances *step_base by
+ * T.  last_val (nullable, [N] float): the value head once more on the observation the rollout ends on (the one left in
+ * b->obs) -- the bootstrap value of b747_ppo_gae, the bits of b747_policy_act's value_out on that observation.  With
+ * n_policies == 1 and rew_pop == NULL every buffer is b747_ppo_rollout_lanes' bit for bit, except val_buf for obs_dim
+ * 3 in FAST (the in-loop head against the batched pass: within the FAST kernels' contraction).  Returns
+ * -hipErrorInvalidValue, with the field named in b747_last_error and before any launch, for everything
+ * b747_ppo_rollout_lanes refuses and for envs_per_policy not a positive multiple of 64, n_policies < 1, N outside
+ * ((n_policies - 1) * envs_per_policy, n_policies * envs_per_policy], policy_stride below
+ * b747_policy_num_params(obs_dim) or not a multiple of 4.  T == 0 validates and launches nothing.  Stream-ordered,
+ * graph-capturable, no allocation. */
+int32_t b747_ppo_rollout_population(const b747_env_batch *b, const b747_env_config *cfg, const b747_consts *c,
+                                    const float *params /* [n_policies][policy_stride] */, int32_t n_policies,
+                                    int64_t policy_stride /* floats */, int32_t envs_per_policy,
+                                    const double *rew_pop /* [n_policies][8], NULL = cfg->rew */,
+                                    uint64_t seed, uint64_t *step_base, int32_t T, float *obs_buf, float *act_buf,
+                                    float *logp_buf, float *val_buf, float *rew_buf, uint8_t *done_buf,
+                                    float *last_val /* [N], nullable */, float act_lo, float act_hi, void *stream);
 int32_t b747_policy_pack(float *params, int32_t obs_dim, void *stream);
 /* noise [N] (nullable): standard-normal draws; NULL = Philox4x32-10 keyed by seed with counter
  * (env_offset + i, *step_base + step); step_base (device, nullable = 0) lets a captured rollout
@@ -448,6 +476,23 @@ int32_t b747_ppo_epoch(float *theta, int32_t obs_dim, const float *obs, const fl
                        double clip_range, double ent_coef, double vf_coef, void *workspace, float *grad,
                        float *m, float *v, int64_t *t, double max_grad_norm, double lr, double beta1, double beta2,
                        double eps, float *stats /* [ceil(n_rows / batch_size)][8] */, void *stream);
+/* One epoch for each of n_policies learners from one call (additive under ABI 15): a host loop over the members of
+ * b747_ppo_epoch's launches -- the same kernels with the same arguments in the same order, so the same bits -- with
+ * member p's theta + p * policy_stride, m / v + p * P, t + p, perm + p * n_rows, lr[p] (a HOST array) and stats + p *
+ * ceil(n_rows / batch_size) * 8.  The rollout buffers are shared: member p's perm row holds global row numbers (for
+ * b747_ppo_rollout_population's layout, t * N + p * envs_per_policy + j).  grad [P] and workspace are reused by every
+ * member.  Everything is validated for every member before the first launch: b747_ppo_epoch's checks, n_policies >= 1,
+ * policy_stride at least b747_policy_num_params(obs_dim) and a multiple of 4, lr != NULL.  No kernel is batched over
+ * members: 4 launches per member and minibatch. */
+int32_t b747_ppo_epoch_population(float *theta /* [n_policies][policy_stride] */, int32_t n_policies,
+                                  int64_t policy_stride, int32_t obs_dim, const float *obs, const float *act,
+                                  const float *old_logp, const float *adv, const float *ret,
+                                  const int64_t *perm /* [n_policies][n_rows] */, int64_t n_rows, int64_t batch_size,
+                                  double clip_range, double ent_coef, double vf_coef, void *workspace,
+                                  float *grad /* [P], reused */, float *m, float *v /* [n_policies][P] */,
+                                  int64_t *t /* [n_policies] */, double max_grad_norm,
+                                  const double *lr /* host, [n_policies] */, double beta1, double beta2, double eps,
+                                  float *stats /* [n_policies][ceil(n_rows / batch_size)][8] */, void *stream);
 
 /* ---- generalized advantage estimation in one launch (ABI 13; PPO.compute_gae, SB3 1.4
  * RolloutBuffer.compute_returns_and_advantage) ----
