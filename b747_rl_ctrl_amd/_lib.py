@@ -101,6 +101,9 @@ SIGNATURES = {
                                     + [_F32, _F32, _V], _I32),
     "b747_ppo_epoch_population": ([_V, _I32, _I64, _I32] + [_V] * 6 + [_I64, _I64, _F64, _F64, _F64] + [_V] * 5
                                   + [_F64, ctypes.POINTER(_F64), _F64, _F64, _F64, _V, _V], _I32),
+    "b747_ppo_epoch_batched_workspace": ([_I32, _I64], _I64),
+    "b747_ppo_epoch_batched": ([_V, _I32, _I64, _I32] + [_V] * 6 + [_I64, _I64, _F64, _F64, _F64, _V, _I64] + [_V] * 3
+                               + [_F64, _V, _F64, _F64, _F64, _V, _V], _I32),
 }
 
 

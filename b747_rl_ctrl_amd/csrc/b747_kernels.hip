@@ -501,6 +501,58 @@ B747_API int32_t b747_ppo_epoch_population(float *theta, int32_t n_policies, int
     return 0;
 }
 
+B747_API int64_t b747_ppo_epoch_batched_workspace(int32_t obs_dim, int64_t batch_size)
+{
+    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("b747_ppo_epoch_batched_workspace: obs_dim (3, 5, 7, 8 or 10)");
+    if (batch_size < 2)
+        return bad_arg("b747_ppo_epoch_batched_workspace: batch_size < 2 (the advantages' standard deviation needs two "
+                       "rows)");
+    return upd_pop_ws_bytes(obs_dim, batch_size);
+}
+
+B747_API int32_t b747_ppo_epoch_batched(float *theta, int32_t n_policies, int64_t policy_stride, int32_t obs_dim,
+                                        const float *obs, const float *act, const float *old_logp, const float *adv,
+                                        const float *ret, const int64_t *perm, int64_t n_rows, int64_t batch_size,
+                                        double clip_range, double ent_coef, double vf_coef, void *workspace,
+                                        int64_t workspace_bytes, float *m, float *v, int64_t *t, double max_grad_norm,
+                                        const double *lr_dev, double beta1, double beta2, double eps, float *stats,
+                                        void *stream)
+{
+    if (!theta) return bad_arg("b747_ppo_epoch_batched: theta is NULL");
+    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("b747_ppo_epoch_batched: obs_dim (3, 5, 7, 8 or 10)");
+    if (n_policies < 1) return bad_arg("b747_ppo_epoch_batched: n_policies < 1");
+    if (policy_stride < policy_total_params(obs_dim) || policy_stride % 4 != 0)
+        return bad_arg("b747_ppo_epoch_batched: policy_stride (at least b747_policy_num_params floats and a multiple "
+                       "of 4)");
+    if (!obs) return bad_arg("b747_ppo_epoch_batched: obs is NULL");
+    if (!act) return bad_arg("b747_ppo_epoch_batched: act is NULL");
+    if (!old_logp) return bad_arg("b747_ppo_epoch_batched: old_logp is NULL");
+    if (!adv) return bad_arg("b747_ppo_epoch_batched: adv is NULL");
+    if (!ret) return bad_arg("b747_ppo_epoch_batched: ret is NULL");
+    if (!perm) return bad_arg("b747_ppo_epoch_batched: perm is NULL");
+    if (n_rows < 2)
+        return bad_arg("b747_ppo_epoch_batched: n_rows < 2 (the advantages' standard deviation needs two rows)");
+    if (batch_size < 2)
+        return bad_arg("b747_ppo_epoch_batched: batch_size < 2 (the advantages' standard deviation needs two rows)");
+    if (n_rows % batch_size == 1)
+        return bad_arg("b747_ppo_epoch_batched: n_rows % batch_size == 1 (the last minibatch would be one row: no "
+                       "standard deviation)");
+    if (!workspace) return bad_arg("b747_ppo_epoch_batched: workspace is NULL");
+    if (workspace_bytes < upd_pop_ws_bytes(obs_dim, batch_size))
+        return bad_arg("b747_ppo_epoch_batched: workspace_bytes (below one member's "
+                       "b747_ppo_epoch_batched_workspace(obs_dim, batch_size))");
+    if (!m) return bad_arg("b747_ppo_epoch_batched: m is NULL");
+    if (!v) return bad_arg("b747_ppo_epoch_batched: v is NULL");
+    if (!t) return bad_arg("b747_ppo_epoch_batched: t is NULL");
+    if (!lr_dev) return bad_arg("b747_ppo_epoch_batched: lr_dev is NULL (a device array, one learning rate per member)");
+    if (!stats) return bad_arg("b747_ppo_epoch_batched: stats is NULL");
+    return launched("b747_ppo_epoch_batched",
+                    launch_ppo_epoch_batched(theta, n_policies, policy_stride, obs_dim, obs, act, old_logp, adv, ret, perm,
+                                             n_rows, batch_size, clip_range, ent_coef, vf_coef, workspace,
+                                             workspace_bytes, m, v, t, max_grad_norm, lr_dev, beta1, beta2, eps, stats,
+                                             (hipStream_t)stream));
+}
+
 B747_API int32_t b747_consts_default(b747_consts *c)
 {
     if (!c) return bad_arg("consts is NULL");

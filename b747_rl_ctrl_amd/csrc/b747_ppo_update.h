@@ -48,6 +48,39 @@ B747_HD constexpr int64_t upd_ws_bytes(int od)
     return upd_ws_grad() + (int64_t)sizeof(float) * PolicyLayout::of(od).total * kUpdMaxWG;
 }
 
+// The member-batched update (b747_ppo_epoch_batched).  Workgroups of k_ppo_grad for a minibatch of
+// `batch` rows: two tiles in flight per workgroup and net, at most one workgroup per CU
+B747_HD constexpr int upd_n_wg(int64_t batch)
+{
+    const int64_t tiles = (batch + kUpdTile - 1) / kUpdTile, want = (tiles + 1) / 2;
+    return (int)(want < kUpdMaxWG ? want : kUpdMaxWG);
+}
+// One member's slice of its workspace (bytes): [adv partials: double 2 x kUpdAdvBlocks][sum partials: double kUpdSums
+// x n_wg][gradient partials: float P x n_wg][the gradient: float P], n_wg = upd_n_wg(batch_size); the slice length
+// is rounded up to 16 bytes
+B747_HD constexpr int64_t upd_pop_ws_grad(int64_t batch_size)
+{
+    return upd_ws_sums() + (int64_t)sizeof(double) * kUpdSums * upd_n_wg(batch_size);
+}
+B747_HD constexpr int64_t upd_pop_ws_out(int od, int64_t batch_size)
+{
+    return upd_pop_ws_grad(batch_size) + (int64_t)sizeof(float) * PolicyLayout::of(od).total * upd_n_wg(batch_size);
+}
+B747_HD constexpr int64_t upd_pop_ws_bytes(int od, int64_t batch_size)
+{
+    return (upd_pop_ws_out(od, batch_size) + (int64_t)sizeof(float) * PolicyLayout::of(od).total + 15) & ~(int64_t)15;
+}
+constexpr int kUpdPopMaxMembers = 65535;   // members of one launch: gridDim.y
+
+// Distances between the members of the k_pop_* kernels (member p = blockIdx.y)
+struct UpdPopArgs {
+    int64_t policy_stride;   // floats: theta
+    int64_t n_params;        // floats: m, v
+    int64_t n_rows;          // int64: perm
+    int64_t ws_stride;       // bytes: the workspace slices
+    int64_t stats_stride;    // floats: the statistics rows of one epoch
+};
+
 // Launchers, defined in b747_ppo_update.hip (hidden: not part of the C ABI).  Arguments are validated by the caller.
 __attribute__((visibility("hidden"))) hipError_t launch_ppo_grad(const float *theta, int od, const float *obs,
                                                                  const float *act, const float *old_logp,
@@ -66,6 +99,15 @@ __attribute__((visibility("hidden"))) hipError_t launch_ppo_epoch(
     const int64_t *perm, int64_t n_rows, int64_t batch_size, double clip_range, double ent_coef, double vf_coef,
     void *workspace, float *grad, float *m, float *v, int64_t *t, double max_grad_norm, double lr, double beta1,
     double beta2, double eps, float *stats, hipStream_t s);
+// One epoch of n_policies members, four launches per minibatch for a whole chunk of members (b747_ppo_epoch_batched):
+// chunks of min(n_policies, workspace_bytes / upd_pop_ws_bytes, kUpdPopMaxMembers) members, each through all its
+// minibatches before the next; lr is a device array; the first launch error ends the loops and is returned
+__attribute__((visibility("hidden"))) hipError_t launch_ppo_epoch_batched(
+    float *theta, int n_policies, int64_t policy_stride, int od, const float *obs, const float *act,
+    const float *old_logp, const float *adv, const float *ret, const int64_t *perm, int64_t n_rows, int64_t batch_size,
+    double clip_range, double ent_coef, double vf_coef, void *workspace, int64_t workspace_bytes, float *m, float *v,
+    int64_t *t, double max_grad_norm, const double *lr, double beta1, double beta2, double eps, float *stats,
+    hipStream_t s);
 
 #ifndef B747_PPO_UPDATE_NO_KERNELS
 
@@ -114,28 +156,17 @@ __device__ __forceinline__ T upd_wave_sum(T x)
 __global__ __launch_bounds__(256) void k_ppo_adv_stats(const float *__restrict__ adv, const int64_t *__restrict__ idx,
                                                        int64_t batch, double *__restrict__ part)
 {
-    __shared__ double red[2][256];
-    const double x0 = (double)adv[idx[0]];
-    double s = 0.0, q = 0.0;
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < batch; j += (int64_t)gridDim.x * 256) {
-        const double d = (double)adv[idx[j]] - x0;
-        s += d;
-        q += d * d;
-    }
-    red[0][threadIdx.x] = s;
-    red[1][threadIdx.x] = q;
-    __syncthreads();
-    for (int w = 128; w >= 1; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + w];
-            red[1][threadIdx.x] += red[1][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = red[0][0];
-        part[2 * blockIdx.x + 1] = red[1][0];
-    }
+    constexpr bool POP = false;
+    constexpr UpdPopArgs pa{0, 0, 0, 0, 0};   // (named by the discarded branch of the body only)
+#include "b747_ppo_adv_stats_body.h"
+}
+
+// k_ppo_adv_stats for every member of a chunk: grid (kUpdAdvBlocks, members).  idx and part are member 0's.
+__global__ __launch_bounds__(256) void k_pop_adv_stats(const float *__restrict__ adv, const int64_t *__restrict__ idx,
+                                                       int64_t batch, double *__restrict__ part, UpdPopArgs pa)
+{
+    constexpr bool POP = true;
+#include "b747_ppo_adv_stats_body.h"
 }
 
 // Accumulators of one net, lane-partial: the dW2 tiles in the C/D layout ([mt][nt]: W2 row 32 mt + C/D row, column
@@ -410,83 +441,24 @@ __global__ __launch_bounds__(256) void k_ppo_grad(const float *__restrict__ thet
                                                   const double *__restrict__ adv_part, float *__restrict__ gpart,
                                                   double *__restrict__ spart)
 {
-    using L = UpdLds<OD>;
-    constexpr PolicyLayout P = PolicyLayout::of(OD);
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ double adv_ms[2];          // mean, 1 / (std + 1e-8)
-    __shared__ double wsum[4][kUpdSums];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr bool POP = false;
+    constexpr UpdPopArgs pa{0, 0, 0, 0, 0};   // (named by the discarded branch of the body only)
+#include "b747_ppo_grad_body.h"
+}
 
-    // ---- stage the parameters
-    for (int e = tid; e < 2 * 2 * 32 * 64; e += 256) {
-        const int net = e >> 12, mt = (e >> 11) & 1, ks = (e >> 6) & 31, l = e & 63;
-        const int w2 = net ? P.vf_w2 : P.pi_w2, u = upd_unit(ks, l >> 5), i = 32 * mt + (l & 31);
-        lds[L::a2 + e] = theta[w2 + i * PH + u];
-        lds[L::t2 + e] = theta[w2 + u * PH + i];
-    }
-    for (int e = tid; e < PH * OD; e += 256) {
-        lds[L::sm + e] = theta[P.pi_w1 + e];
-        lds[L::sm + L::net + e] = theta[P.vf_w1 + e];
-    }
-    if (tid < PH) {
-        float *p0 = lds + L::sm + PH * OD, *p1 = p0 + L::net;
-        p0[tid] = theta[P.pi_b1 + tid];
-        p0[PH + tid] = theta[P.pi_b2 + tid];
-        p0[2 * PH + tid] = theta[P.wa + tid];
-        p1[tid] = theta[P.vf_b1 + tid];
-        p1[PH + tid] = theta[P.vf_b2 + tid];
-        p1[2 * PH + tid] = theta[P.wv + tid];
-    }
-    if (tid == 64) {
-        lds[L::hb] = theta[P.ba];
-        lds[L::hb + 1] = theta[P.bv];
-        lds[L::ls] = theta[P.log_std];
-    }
-    if (tid == 0) {   // the minibatch's advantage statistics from the blocks' partial sums, in block order
-        double s = 0.0, q = 0.0;
-        for (int b = 0; b < kUpdAdvBlocks; ++b) {
-            s += adv_part[2 * b];
-            q += adv_part[2 * b + 1];
-        }
-        const double n = (double)batch, var = (q - s * s / n) / (n - 1.0);
-        adv_ms[0] = (double)adv[idx[0]] + s / n;
-        adv_ms[1] = 1.0 / (sqrt(var > 0.0 ? var : 0.0) + 1e-8);
-    }
-    __syncthreads();
-
-    // waves 0 / 1 take the policy net, waves 2 / 3 the value net (one net's accumulators per wave); each pair of
-    // waves walks every tile of the workgroup's share
-    float *wv = lds + L::wave + wave * L::per_wave;
-    UpdNetAcc<OD> acc;
-    acc.zero();
-    double sums[kUpdSums] = {};
-    const UpdRowArgs ra{obs, act, old_logp, adv, ret, idx, batch, clip, vf_coef, adv_ms[0], adv_ms[1]};
-    if (wave < 2) upd_tiles<OD, 0>(lds, wv, ra, lane, blockIdx.x * 2 + (wave & 1), gridDim.x * 2, acc, sums);
-    else upd_tiles<OD, 1>(lds, wv, ra, lane, blockIdx.x * 2 + (wave & 1), gridDim.x * 2, acc, sums);
-
-    // ---- the waves' accumulators into one vector (waves 0 and 2 store their net's part, then 1 and 3 add theirs)
-    __syncthreads();                     // every wave is done with the fragments: their region becomes the vector
-#pragma unroll 1
-    for (int w = 0; w < 2; ++w) {
-        if ((wave & 1) == w) {
-            if (wave < 2) {
-                upd_flush<OD, 0>(lds, lane, acc, w == 0);
-                if (lane == 0 && w == 0) lds[P.log_std] = 0.0f;
-            } else {
-                upd_flush<OD, 1>(lds, lane, acc, w == 0);
-            }
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < kUpdSums; ++k) {
-        const double v = upd_wave_sum(sums[k]);
-        if (lane == 0) wsum[wave][k] = v;
-    }
-    __syncthreads();
-    for (int e = tid; e < P.total; e += 256) gpart[(int64_t)blockIdx.x * P.total + e] = lds[e];
-    if (tid < kUpdSums)
-        spart[blockIdx.x * kUpdSums + tid] = ((wsum[0][tid] + wsum[1][tid]) + wsum[2][tid]) + wsum[3][tid];
+// k_ppo_grad<OD> for every member of a chunk: grid (n_wg, members), n_wg what the member's own launch has.  theta,
+// idx and the three workspace pointers are member 0's.
+template <int OD>
+__global__ __launch_bounds__(256) void k_pop_grad(const float *__restrict__ theta, const float *__restrict__ obs,
+                                                  const float *__restrict__ act, const float *__restrict__ old_logp,
+                                                  const float *__restrict__ adv, const float *__restrict__ ret,
+                                                  const int64_t *__restrict__ idx, int64_t batch, double clip,
+                                                  double vf_coef,
+                                                  const double *__restrict__ adv_part, float *__restrict__ gpart,
+                                                  double *__restrict__ spart, UpdPopArgs pa)
+{
+    constexpr bool POP = true;
+#include "b747_ppo_grad_body.h"
 }
 
 // grad[i] = the partials' sum in workgroup order (fp64, rounded once); the last thread turns the row sums into
@@ -496,35 +468,21 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(const float *__restrict__ gp
                                                     const float *__restrict__ theta, int64_t batch, float ent_coef,
                                                     float vf_coef, float *__restrict__ grad, float *__restrict__ stats)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n_params) {
-        double a = 0.0;
-        const int k = i == ba_at ? 6 : (i == bv_at ? 7 : (i == log_std_at ? 8 : -1));   // the three fp64 sums
-        if (k >= 0) {
-            for (int w = 0; w < n_wg; ++w) a += spart[w * kUpdSums + k];
-        } else {
-#pragma unroll 8
-            for (int w = 0; w < n_wg; ++w) a += (double)gpart[(int64_t)w * n_params + i];
-        }
-        if (i == log_std_at) a -= (double)ent_coef;
-        grad[i] = (float)a;
-    } else if (i == n_params) {
-        double s[kUpdSums] = {};
-        for (int w = 0; w < n_wg; ++w)
-#pragma unroll
-            for (int k = 0; k < kUpdSums; ++k) s[k] += spart[w * kUpdSums + k];
-        const double n = (double)batch;
-        const float pg = (float)(-s[0] / n), vfl = (float)(s[1] / n);
-        const float ent = -((0.5f + 0.918938533204672742f) + theta[log_std_at]);
-        stats[0] = pg;
-        stats[1] = vfl;
-        stats[2] = ent;
-        stats[3] = (float)(s[2] / n);
-        stats[4] = (float)(s[3] / n);
-        stats[5] = (float)(s[4] / n);
-        stats[6] = (float)(s[5] / n);
-        stats[7] = (pg + ent_coef * ent) + vf_coef * vfl;
-    }
+    constexpr bool POP = false;
+    constexpr UpdPopArgs pa{0, 0, 0, 0, 0};   // (named by the discarded branch of the body only)
+#include "b747_ppo_reduce_body.h"
+}
+
+// k_ppo_reduce for every member of a chunk: grid (ceil((n_params + 1) / 256), members).  gpart, spart, grad (in the
+// workspace), theta and stats are member 0's.
+__global__ __launch_bounds__(256) void k_pop_reduce(const float *__restrict__ gpart, const double *__restrict__ spart,
+                                                    int n_wg, int n_params, int ba_at, int bv_at, int log_std_at,
+                                                    const float *__restrict__ theta, int64_t batch, float ent_coef,
+                                                    float vf_coef, float *__restrict__ grad, float *__restrict__ stats,
+                                                    UpdPopArgs pa)
+{
+    constexpr bool POP = true;
+#include "b747_ppo_reduce_body.h"
 }
 
 // clip_grad_norm_ + torch.optim.Adam (no weight decay, no amsgrad) on the flat vector: g = grad_scale grad,
@@ -536,34 +494,22 @@ __global__ __launch_bounds__(kUpdAdamBlock) void k_ppo_adam(float *__restrict__ 
                                                             double max_norm, double lr, double beta1, double beta2,
                                                             double eps)
 {
-    __shared__ double red[kUpdAdamBlock];
-    const int tid = threadIdx.x;
-    const int64_t step = t[0] + 1;
-    double q = 0.0;
-    for (int64_t i = tid; i < n; i += kUpdAdamBlock) {
-        const double g = (double)(float)(grad_scale * (double)grad[i]);
-        q += g * g;
-    }
-    red[tid] = q;
-    __syncthreads();
-    for (int w = kUpdAdamBlock / 2; w >= 1; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    const double norm = sqrt(red[0]);
-    const double c0 = max_norm / (norm + 1e-6), coef = c0 < 1.0 ? c0 : 1.0;
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2s = sqrt(1.0 - pow(beta2, (double)step));
-    const double step_size = lr / bc1;
-    for (int64_t i = tid; i < n; i += kUpdAdamBlock) {
-        const double g = (double)(float)((double)(float)(grad_scale * (double)grad[i]) * coef);
-        const double mi = (double)m[i] + (1.0 - beta1) * (g - (double)m[i]);
-        const double vi = beta2 * (double)v[i] + (1.0 - beta2) * g * g;
-        const float mf = (float)mi, vf = (float)vi;
-        m[i] = mf;
-        v[i] = vf;
-        theta[i] = (float)((double)theta[i] - step_size * ((double)mf / (sqrt((double)vf) / bc2s + eps)));
-    }
-    if (tid == 0) t[0] = step;   // (every thread read the old count before the first barrier)
+    constexpr bool POP = false;
+    constexpr UpdPopArgs pa{0, 0, 0, 0, 0};   // (named by the discarded branch of the body only)
+#include "b747_ppo_adam_body.h"
+}
+
+// k_ppo_adam for every member of a chunk: grid (1, members), one workgroup per member.  theta, m, v, t, grad (in the
+// workspace) and lr_dev are member 0's; the member's learning rate comes from the device array.
+__global__ __launch_bounds__(kUpdAdamBlock) void k_pop_adam(float *__restrict__ theta, float *__restrict__ m,
+                                                            float *__restrict__ v, int64_t *__restrict__ t,
+                                                            const float *__restrict__ grad, int64_t n, double grad_scale,
+                                                            double max_norm, const double *__restrict__ lr_dev,
+                                                            double beta1, double beta2, double eps, UpdPopArgs pa)
+{
+    constexpr bool POP = true;
+    const double lr = lr_dev[blockIdx.y];
+#include "b747_ppo_adam_body.h"
 }
 
 #endif  // B747_PPO_UPDATE_NO_KERNELS

@@ -68,6 +68,54 @@ hipError_t epoch_od(float *theta, const float *obs, const float *act, const floa
     return hipSuccess;
 }
 
+// b747_ppo_epoch_batched's loops: members in chunks of as many slices as the workspace holds; a chunk's minibatch j is
+// the four launches of epoch_od's minibatch j with the members on blockIdx.y.  The pointers passed are those of the
+// chunk's first member; the kernels add the member's distance (UpdPopArgs).
+template <int OD>
+hipError_t epoch_batched_od(float *theta, int n_policies, int64_t policy_stride, const float *obs, const float *act,
+                            const float *old_logp, const float *adv, const float *ret, const int64_t *perm,
+                            int64_t n_rows, int64_t batch_size, double clip_range, double ent_coef, double vf_coef,
+                            void *workspace, int64_t workspace_bytes, float *m, float *v, int64_t *t,
+                            double max_grad_norm, const double *lr, double beta1, double beta2, double eps, float *stats,
+                            hipStream_t s)
+{
+    constexpr PolicyLayout L = PolicyLayout::of(OD);
+    constexpr int P = L.total;
+    const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pop_grad<OD>),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, UpdLds<OD>::bytes);
+    if (attr != hipSuccess) return attr;
+    const int64_t per = upd_pop_ws_bytes(OD, batch_size), n_mb = (n_rows + batch_size - 1) / batch_size;
+    int64_t chunk = workspace_bytes / per;
+    if (chunk > n_policies) chunk = n_policies;
+    if (chunk > kUpdPopMaxMembers) chunk = kUpdPopMaxMembers;
+    const UpdPopArgs pa{policy_stride, P, n_rows, per, n_mb * kUpdStats};
+    char *ws = static_cast<char *>(workspace);
+    double *adv_part = reinterpret_cast<double *>(ws + upd_ws_adv());
+    double *spart = reinterpret_cast<double *>(ws + upd_ws_sums());
+    float *gpart = reinterpret_cast<float *>(ws + upd_pop_ws_grad(batch_size));
+    float *grad = reinterpret_cast<float *>(ws + upd_pop_ws_out(OD, batch_size));
+    for (int64_t c0 = 0; c0 < n_policies; c0 += chunk) {
+        const unsigned members = (unsigned)(n_policies - c0 < chunk ? n_policies - c0 : chunk);
+        float *th = theta + c0 * policy_stride, *st = stats + c0 * n_mb * kUpdStats;
+        const int64_t *pm = perm + c0 * n_rows;
+        for (int64_t at = 0; at < n_rows; at += batch_size, st += kUpdStats) {
+            const int64_t batch = n_rows - at < batch_size ? n_rows - at : batch_size;
+            const int n_wg = upd_n_wg(batch);
+            hipLaunchKernelGGL(k_pop_adv_stats, dim3(kUpdAdvBlocks, members), dim3(256), 0, s, adv, pm + at, batch,
+                               adv_part, pa);
+            hipLaunchKernelGGL(k_pop_grad<OD>, dim3(n_wg, members), dim3(256), UpdLds<OD>::bytes, s, th, obs, act, old_logp,
+                               adv, ret, pm + at, batch, clip_range, vf_coef, adv_part, gpart, spart, pa);
+            hipLaunchKernelGGL(k_pop_reduce, dim3((P + 1 + 255) / 256, members), dim3(256), 0, s, gpart, spart, n_wg, P,
+                               L.ba, L.bv, L.log_std, th, batch, (float)ent_coef, (float)vf_coef, grad, st, pa);
+            hipLaunchKernelGGL(k_pop_adam, dim3(1, members), dim3(kUpdAdamBlock), 0, s, th, m + c0 * P, v + c0 * P, t + c0,
+                               grad, (int64_t)P, 1.0, max_grad_norm, lr + c0, beta1, beta2, eps, pa);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
 }  // namespace
 
 hipError_t launch_ppo_grad(const float *theta, int od, const float *obs, const float *act, const float *old_logp,
@@ -117,6 +165,29 @@ hipError_t launch_ppo_epoch(float *theta, int od, const float *obs, const float 
     default: return hipErrorInvalidValue;
     }
 #undef B747_EPOCH
+}
+
+hipError_t launch_ppo_epoch_batched(float *theta, int n_policies, int64_t policy_stride, int od, const float *obs,
+                                    const float *act, const float *old_logp, const float *adv, const float *ret,
+                                    const int64_t *perm, int64_t n_rows, int64_t batch_size, double clip_range,
+                                    double ent_coef, double vf_coef, void *workspace, int64_t workspace_bytes, float *m,
+                                    float *v, int64_t *t, double max_grad_norm, const double *lr, double beta1,
+                                    double beta2, double eps, float *stats, hipStream_t s)
+{
+#define B747_EPOCH_BATCHED(OD)                                                                                        \
+    case OD:                                                                                                          \
+        return epoch_batched_od<OD>(theta, n_policies, policy_stride, obs, act, old_logp, adv, ret, perm, n_rows,     \
+                                    batch_size, clip_range, ent_coef, vf_coef, workspace, workspace_bytes, m, v, t,   \
+                                    max_grad_norm, lr, beta1, beta2, eps, stats, s)
+    switch (od) {
+        B747_EPOCH_BATCHED(3);
+        B747_EPOCH_BATCHED(5);
+        B747_EPOCH_BATCHED(7);
+        B747_EPOCH_BATCHED(8);
+        B747_EPOCH_BATCHED(10);
+    default: return hipErrorInvalidValue;
+    }
+#undef B747_EPOCH_BATCHED
 }
 
 }  // namespace b747

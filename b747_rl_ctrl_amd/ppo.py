@@ -583,10 +583,21 @@ class PopulationPPO:
     (b747_ppo_epoch_population): the same kernels, the same bits as P separate learners
     (tests/test_gpu_ppo_population_train.py).  `seed` keys the action noise (Philox counters (seed, step, global env
     id), shared by the members, whose env ids differ).  No torch modules are kept: `flat` [P, stride] is the master copy
-    of every member's parameters (member(p) gives an ActorCritic copy)."""
+    of every member's parameters (member(p) gives an ActorCritic copy).
+
+    batched_update=True (opt-in) makes the epoch call b747_ppo_epoch_batched: four launches per minibatch
+    for all members (the member on blockIdx.y of member-batched update kernels) in place of four per member -- the same
+    bits (tests/test_gpu_ppo_population_batched_train.py), a workspace slice per member instead of one shared."""
+
+    # The batched update's workspace holds one slice per member (b747_ppo_epoch_batched_workspace: ~9 MB at the full
+    # 256-workgroup grid, ~80 kB at batch 256) so that all members run in one launch; past this many bytes the call
+    # works through the members in chunks of as many slices as fit, which changes no bit and costs four launches
+    # per chunk and minibatch instead of four per minibatch.
+    BATCHED_WORKSPACE_CAP = 1 << 30
 
     def __init__(self, env: BatchControllerEnv, n_members: int, envs_per_member: int = 64,
-                 cfg: Optional[PPOConfig] = None, seeds=None, rew_configs=None, learning_rates=None, seed: int = 0):
+                 cfg: Optional[PPOConfig] = None, seeds=None, rew_configs=None, learning_rates=None, seed: int = 0,
+                 batched_update: bool = False):
         from . import _lib
         from .evaluate import pack_policies
         self._lib, self._L = _lib, _lib.lib()
@@ -620,6 +631,14 @@ class PopulationPPO:
         if ws <= 0:
             raise ValueError(f"PopulationPPO does not cover this policy: {self._L.b747_last_error().decode()}")
         self.upd_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
+        self.batched_update = bool(batched_update)
+        if self.batched_update:
+            per = int(self._L.b747_ppo_epoch_batched_workspace(od, self.cfg.batch_size))
+            if per <= 0:
+                raise ValueError(f"PopulationPPO(batched_update=True): {self._L.b747_last_error().decode()}")
+            self.lr_dev = torch.tensor(lrs, dtype=torch.float64, device=dev)      # b747_ppo_epoch_batched reads them there
+            self.upd_ws_batched = torch.empty(max(1, min(P, self.BATCHED_WORKSPACE_CAP // per)) * per, dtype=torch.uint8,
+                                              device=dev)
         self.obs_buf, self.act_buf = z(T, n, od), z(T, n, 1)
         self.logp_buf, self.val_buf, self.rew_buf = z(T, n), z(T, n), z(T, n)
         self.done_buf = z(T, n, dt=torch.bool)
@@ -666,7 +685,8 @@ class PopulationPPO:
     def train(self, T: Optional[int] = None,
               minibatch_order: Optional[Callable[[int, int, int, int], torch.Tensor]] = None):
         """PPO.train(fused_update, epoch_call) for every member: per epoch one sample order per member and ONE
-        b747_ppo_epoch_population call; afterwards one b747_policy_pack_batch.
+        b747_ppo_epoch_population call (b747_ppo_epoch_batched with batched_update); afterwards one
+        b747_policy_pack_batch.
         minibatch_order(epoch, T, envs_per_member, p) -> [T * envs_per_member] indices into MEMBER p's own time-major
         rows (t * envs_per_member + j: what PPO.train's hook gives a learner that has the member's envs to itself);
         default torch.randperm.  Returns PPO.train's names as [P] tensors (float64; explained_variance and std
@@ -686,6 +706,14 @@ class PopulationPPO:
                                      for m in range(P)])
             assert tuple(local.shape) == (P, n_rows), "minibatch_order must give every row of the member once"
             perm = torch.gather(rows_of, 1, local).contiguous()       # member rows -> rows t * N + i of the buffers
+            if self.batched_update:
+                self._lib.check(self._L.b747_ppo_epoch_batched(
+                    p(self.flat), P, self.stride, self.env.obs_dim, p(self.obs_buf), p(self.act_buf), p(self.logp_buf),
+                    p(self.adv_buf), p(self.ret_buf), p(perm), n_rows, c.batch_size, c.clip_range, c.ent_coef, c.vf_coef,
+                    p(self.upd_ws_batched), self.upd_ws_batched.numel(), p(self.upd_m), p(self.upd_v), p(self.upd_t),
+                    c.max_grad_norm, p(self.lr_dev), 0.9, 0.999, 1e-5, p(stats[epoch]),
+                    torch.cuda.current_stream().cuda_stream), "b747_ppo_epoch_batched")
+                continue
             self._lib.check(self._L.b747_ppo_epoch_population(
                 p(self.flat), P, self.stride, self.env.obs_dim, p(self.obs_buf), p(self.act_buf), p(self.logp_buf),
                 p(self.adv_buf), p(self.ret_buf), p(perm), n_rows, c.batch_size, c.clip_range, c.ent_coef, c.vf_coef,

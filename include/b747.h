@@ -38,7 +38,8 @@ extern "C" {
                                 * (it holds float32 values; 8 B less per env step); 11: + b747_eval_episodes;
                                 * 12: + b747_ppo_update_workspace, b747_ppo_grad, b747_ppo_adam; 13: + b747_ppo_gae,
                                 * b747_ppo_epoch, b747_get_specialization; 14: + b747_ppo_rollout_lanes; 15: + b747_eval_population,
-                                * b747_policy_pack_batch.  b747_ppo_rollout_population and b747_ppo_epoch_population
+                                * b747_policy_pack_batch.  b747_ppo_rollout_population, b747_ppo_epoch_population,
+                                * b747_ppo_epoch_batched_workspace and b747_ppo_epoch_batched
                                 * came later as purely additive entry points under 15 (no struct, argument or
                                 * behaviour of an existing one changed): a library built before them still reports
                                 * 15, and a binding catches it by the missing entry point (_lib.bind) */
@@ -493,6 +494,31 @@ int32_t b747_ppo_epoch_population(float *theta /* [n_policies][policy_stride] */
                                   int64_t *t /* [n_policies] */, double max_grad_norm,
                                   const double *lr /* host, [n_policies] */, double beta1, double beta2, double eps,
                                   float *stats /* [n_policies][ceil(n_rows / batch_size)][8] */, void *stream);
+/* b747_ppo_epoch_population with the kernels batched over members (additive under ABI 15): per minibatch
+ * FOUR launches for a whole chunk of members -- member-batched siblings of the four update kernels, the member on
+ * blockIdx.y, each running the single-member kernel's text on its member's pointers, with the grid x extent, the tile
+ * assignment and every summation order of the member's own launch -- so theta, m, v, t and stats get the bits of
+ * b747_ppo_epoch_population.  Differences in the arguments: no grad (each member's gradient vector lives in its slice
+ * of the workspace); lr_dev is a DEVICE array [n_policies]; workspace_bytes says how much workspace there is.
+ * b747_ppo_epoch_batched_workspace(obs_dim, batch_size): bytes PER MEMBER, 1024 + 72 n_wg + 4 P (n_wg + 1) rounded up
+ * to a multiple of 16, with n_wg = min(256, ceil(ceil(batch_size / 32) / 2)) and P = 128 obs_dim + 8579 (2 x 64 fp64
+ * advantage partials, 9 x n_wg fp64 row sums, n_wg partial gradient vectors, the gradient vector);
+ * -hipErrorInvalidValue for an unsupported obs_dim or batch_size < 2.
+ * Members are processed in chunks of min(n_policies, workspace_bytes / per member, 65535 -- a grid's y extent): a chunk
+ * runs all its minibatches, then the next chunk starts.  Members are independent, so the chunking changes no bit; a
+ * workspace for all members means the fewest launches.  workspace: 16-byte aligned, the caller's, its contents mean
+ * nothing between calls.  Everything is validated before the first launch: b747_ppo_epoch_population's checks,
+ * workspace_bytes at least one member's, lr_dev != NULL; -hipErrorInvalidValue with the argument named in
+ * b747_last_error.  Stream-ordered, graph-capturable, allocates nothing, synchronises nothing, reads nothing back. */
+int64_t b747_ppo_epoch_batched_workspace(int32_t obs_dim, int64_t batch_size);
+int32_t b747_ppo_epoch_batched(float *theta /* [n_policies][policy_stride] */, int32_t n_policies, int64_t policy_stride,
+                               int32_t obs_dim, const float *obs, const float *act, const float *old_logp,
+                               const float *adv, const float *ret, const int64_t *perm /* [n_policies][n_rows] */,
+                               int64_t n_rows, int64_t batch_size, double clip_range, double ent_coef, double vf_coef,
+                               void *workspace, int64_t workspace_bytes, float *m, float *v /* [n_policies][P] */,
+                               int64_t *t /* [n_policies] */, double max_grad_norm,
+                               const double *lr_dev /* device, [n_policies] */, double beta1, double beta2, double eps,
+                               float *stats /* [n_policies][ceil(n_rows / batch_size)][8] */, void *stream);
 
 /* ---- generalized advantage estimation in one launch (ABI 13; PPO.compute_gae, SB3 1.4
  * RolloutBuffer.compute_returns_and_advantage) ----
