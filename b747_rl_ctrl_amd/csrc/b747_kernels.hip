@@ -16,6 +16,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
+
 #include "../../include/b747.h"
 #include "b747_dynamics.h"
 #include "b747_env.h"
@@ -42,11 +44,14 @@ int32_t fail(hipError_t e, const char *where)
     return -(int32_t)e;
 }
 
-int32_t bad_arg(const char *what)
+// where: the entry point's name in front of the message, or nullptr for the older entry points, whose messages carry none
+int32_t bad_arg(const char *where, const char *what)
 {
-    snprintf(g_err, sizeof(g_err), "invalid argument: %s", what);
+    if (where) snprintf(g_err, sizeof(g_err), "invalid argument: %s: %s", where, what);
+    else snprintf(g_err, sizeof(g_err), "invalid argument: %s", what);
     return -(int32_t)hipErrorInvalidValue;
 }
+int32_t bad_arg(const char *what) { return bad_arg(nullptr, what); }
 
 // the tail of every entry point that launches: 0, or the launch's error under the entry point's name
 int32_t launched(const char *where, hipError_t e = hipGetLastError()) { return e == hipSuccess ? 0 : fail(e, where); }
@@ -104,7 +109,112 @@ template __global__ void k_env_steps<double, false, 1, true>(b747_env_batch, b74
 template __global__ void k_env_steps<float, false, 1, true>(b747_env_batch, b747_env_config, Consts, const float *,
                                                            int32_t, float *, float *, uint8_t *);
 
-bool policy_obs_dim_ok(int32_t od) { return od == 3 || od == 5 || od == 7 || od == 8 || od == 10; }
+// The validators below are shared by the entry points of one family: 0, or bad_arg's code with the message under
+// `where` (nullptr: no name).  The order of the checks is part of the ABI: it decides the message of a doubly-wrong call.
+
+// "<name> is NULL" for the first null pointer of the list
+struct NamedPtr {
+    const void *p;
+    const char *name;
+};
+int32_t check_not_null(const char *where, std::initializer_list<NamedPtr> ptrs)
+{
+    char what[64];
+    for (const NamedPtr &a : ptrs) {
+        if (a.p) continue;
+        snprintf(what, sizeof(what), "%s is NULL", a.name);
+        return bad_arg(where, what);
+    }
+    return 0;
+}
+
+bool policy_stride_ok(int64_t policy_stride, int32_t od)
+{
+    return policy_stride >= policy_total_params(od) && policy_stride % 4 == 0;
+}
+
+// --- the update family (b747_ppo_grad, _epoch, _epoch_population, _epoch_batched), in three parts around the entry
+// points' own checks: the policy; the members; the rows (epoch false: b747_ppo_grad's one minibatch `idx` of n_rows)
+int32_t check_upd_policy(const char *where, const float *theta, int32_t obs_dim)
+{
+    if (!theta) return bad_arg(where, "theta is NULL");
+    if (!policy_obs_dim_ok(obs_dim)) return bad_arg(where, "obs_dim (3, 5, 7, 8 or 10)");
+    return 0;
+}
+int32_t check_upd_members(const char *where, int32_t n_policies, int64_t policy_stride, int32_t obs_dim)
+{
+    if (n_policies < 1) return bad_arg(where, "n_policies < 1");
+    if (!policy_stride_ok(policy_stride, obs_dim))
+        return bad_arg(where, "policy_stride (at least b747_policy_num_params floats and a multiple of 4)");
+    return 0;
+}
+int32_t check_upd_rows(const char *where, const UpdData &d, const int64_t *idx, bool epoch, int64_t n_rows,
+                       int64_t batch_size, const void *workspace)
+{
+    if (int32_t e = check_not_null(where, {{d.obs, "obs"}, {d.act, "act"}, {d.old_logp, "old_logp"}, {d.adv, "adv"},
+                                           {d.ret, "ret"}, {idx, epoch ? "perm" : "idx"}}))
+        return e;
+    if (!epoch) {
+        if (n_rows < 2) return bad_arg(where, "batch < 2 (the advantages' standard deviation needs two rows)");
+    } else {
+        if (n_rows < 2) return bad_arg(where, "n_rows < 2 (the advantages' standard deviation needs two rows)");
+        if (batch_size < 2) return bad_arg(where, "batch_size < 2 (the advantages' standard deviation needs two rows)");
+        if (n_rows % batch_size == 1)
+            return bad_arg(where, "n_rows % batch_size == 1 (the last minibatch would be one row: no standard deviation)");
+    }
+    return check_not_null(where, {{workspace, "workspace"}});
+}
+
+// --- the population tiling (b747_eval_population, b747_ppo_rollout_population), in two parts: the groups, then -- once
+// the batch is known not to be empty -- the batch's place in them and the parameter sets' distance
+int32_t check_pop_groups(const char *where, int32_t envs_per_policy, int32_t n_policies, const char *few_policies)
+{
+    if (envs_per_policy < 64 || envs_per_policy % 64 != 0)
+        return bad_arg(where, "envs_per_policy (a positive multiple of 64: a wave flies one policy)");
+    if (n_policies < 1) return bad_arg(where, few_policies);
+    return 0;
+}
+int32_t check_pop_tiling(const char *where, const b747_env_batch &b, int32_t n_policies, int32_t envs_per_policy,
+                         int64_t policy_stride)
+{
+    if (b.n <= (int64_t)(n_policies - 1) * envs_per_policy || b.n > (int64_t)n_policies * envs_per_policy)
+        return bad_arg(where, "n (outside ((n_policies - 1) * envs_per_policy, n_policies * envs_per_policy])");
+    if (!policy_stride_ok(policy_stride, b.obs_dim))
+        return bad_arg(where, "policy_stride (at least b747_policy_num_params floats and a multiple of 4: the fragments "
+                              "start on a 16-byte boundary)");
+    return 0;
+}
+
+// --- the rollout buffers (b747_ppo_rollout_lanes, b747_ppo_rollout_population)
+int32_t check_rollout_args(const char *where, const b747_consts *c, const RolloutLanesArgs &ra)
+{
+    if (int32_t e = check_not_null(where, {{c, "consts"}, {ra.params, "params"}, {ra.obs_buf, "obs_buf"},
+                                           {ra.act_buf, "act_buf"}, {ra.logp_buf, "logp_buf"}, {ra.val_buf, "val_buf"},
+                                           {ra.rew_buf, "rew_buf"}, {ra.done_buf, "done_buf"}}))
+        return e;
+    if (ra.T < 0) return bad_arg(where, "T < 0");
+    if (!(ra.act_lo <= ra.act_hi)) return bad_arg(where, "act_lo > act_hi");
+    return 0;
+}
+
+// --- the step-response arguments (b747_eval_episodes, b747_eval_population).  b747_eval_episodes names itself in the
+// messages about the batch only: `where` is nullptr there, `name` the entry point's in both
+int32_t check_eval_args(const char *where, const char *name, const b747_env_batch &b, const b747_env_config &cfg,
+                        const b747_consts *c, const EvalArgs &ea)
+{
+    if (!c) return bad_arg(where, "consts is NULL");
+    if (!ea.y_base || !ea.out) return bad_arg(where, "y_base / eval_out is NULL");
+    if (ea.n_env_steps < 0) return bad_arg(where, "n_env_steps < 0");
+    if (ea.sig_row < 0 || ea.sig_row >= B747_NSIG) return bad_arg(where, "sig_row (a B747_SIG_* row)");
+    if (!(ea.act_lo <= ea.act_hi)) return bad_arg(where, "act_lo > act_hi");
+    if (!b.x_f64) return bad_arg(name, "x_f64 (the episode kernel keeps fp64 state only)");
+    if (cfg.auto_reset != 0) return bad_arg(name, "auto_reset must be 0 (an episode ends at its first done)");
+    if (ea.params && b.obs_dim != 3 && b.obs_dim != 5)
+        return bad_arg(name, "obs_dim (a policy runs with PID_LIKE 3 or SPEED_MODE 5 only; other observation types take "
+                             "params = NULL)");
+    if (!ea.params && !b.action) return bad_arg(name, "action is NULL (params = NULL holds b->action)");
+    return 0;
+}
 
 }  // namespace
 
@@ -152,19 +262,12 @@ B747_API int32_t b747_policy_act(const float *params, int32_t obs_dim, int64_t n
     if (!(act_lo <= act_hi)) return bad_arg("act_lo > act_hi");
     hipStream_t s = (hipStream_t)stream;
     const dim3 g(grid_for(n)), blk(kBlock);
-#define B747_LAUNCH_POLICY(OD)                                                                               \
-    hipLaunchKernelGGL(k_policy_act<OD>, g, blk, 0, s, params, n, obs, noise, seed, step_base, step, env_offset, \
-                       obs_out, \
-                       act_out, logp_out, value_out, env_action, act_lo, act_hi)
-    switch (obs_dim) {
-    case 3: B747_LAUNCH_POLICY(3); break;
-    case 5: B747_LAUNCH_POLICY(5); break;
-    case 7: B747_LAUNCH_POLICY(7); break;
-    case 8: B747_LAUNCH_POLICY(8); break;
-    case 10: B747_LAUNCH_POLICY(10); break;
-    default: return bad_arg("obs_dim (PID_LIKE 3, SPEED_MODE 5, MODEL_STATE 7, PID_AERO 8, PID_SPEED_AERO 10)");
-    }
-#undef B747_LAUNCH_POLICY
+    const bool known = with_obs_dim(obs_dim, false, [&](auto OD) {
+        hipLaunchKernelGGL(k_policy_act<OD()>, g, blk, 0, s, params, n, obs, noise, seed, step_base, step, env_offset,
+                           obs_out, act_out, logp_out, value_out, env_action, act_lo, act_hi);
+        return true;
+    });
+    if (!known) return bad_arg("obs_dim (PID_LIKE 3, SPEED_MODE 5, MODEL_STATE 7, PID_AERO 8, PID_SPEED_AERO 10)");
     return launched("b747_policy_act");
 }
 
@@ -201,21 +304,12 @@ B747_API int32_t b747_ppo_rollout_lanes(const b747_env_batch *b, const b747_env_
 {
     int32_t r = check_env(b, cfg);
     if (r < 0) return r;
-    if (!c) return bad_arg("b747_ppo_rollout_lanes: consts is NULL");
-    if (!params) return bad_arg("b747_ppo_rollout_lanes: params is NULL");
-    if (!obs_buf) return bad_arg("b747_ppo_rollout_lanes: obs_buf is NULL");
-    if (!act_buf) return bad_arg("b747_ppo_rollout_lanes: act_buf is NULL");
-    if (!logp_buf) return bad_arg("b747_ppo_rollout_lanes: logp_buf is NULL");
-    if (!val_buf) return bad_arg("b747_ppo_rollout_lanes: val_buf is NULL");
-    if (!rew_buf) return bad_arg("b747_ppo_rollout_lanes: rew_buf is NULL");
-    if (!done_buf) return bad_arg("b747_ppo_rollout_lanes: done_buf is NULL");
-    if (T < 0) return bad_arg("b747_ppo_rollout_lanes: T < 0");
-    if (!(act_lo <= act_hi)) return bad_arg("b747_ppo_rollout_lanes: act_lo > act_hi");
+    const RolloutLanesArgs ra{params, seed, step_base, T, act_lo, act_hi, obs_buf, act_buf, logp_buf, val_buf, rew_buf,
+                              done_buf};
+    if (int32_t e = check_rollout_args("b747_ppo_rollout_lanes", c, ra)) return e;
     if (r == 0) return 0;   // an empty batch
     if (const char *why = ppo_rollout_lanes_refusal(*b)) return bad_arg(why);
     if (T == 0) return 0;
-    const RolloutLanesArgs ra{params, seed, step_base, T, act_lo, act_hi, obs_buf, act_buf, logp_buf, val_buf, rew_buf,
-                              done_buf};
     const Consts C = consts_of(c);   // run-time constants, as the evaluation kernel
     // (the launcher's second launch advances *step_base by T: ordered after the rollout kernel's last read of it;
     //  where the value head is deferred, b747_ppo_rollout's value pass does both)
@@ -239,20 +333,9 @@ B747_API int32_t b747_eval_episodes(const b747_env_batch *b, const b747_env_conf
 {
     int32_t r = check_env(b, cfg);
     if (r <= 0) return r;
-    if (!c) return bad_arg("consts is NULL");
-    if (!y_base || !eval_out) return bad_arg("y_base / eval_out is NULL");
-    if (n_env_steps < 0) return bad_arg("n_env_steps < 0");
-    if (sig_row < 0 || sig_row >= B747_NSIG) return bad_arg("sig_row (a B747_SIG_* row)");
-    if (!(act_lo <= act_hi)) return bad_arg("act_lo > act_hi");
-    if (!b->x_f64) return bad_arg("b747_eval_episodes: x_f64 (the episode kernel keeps fp64 state only)");
-    if (cfg->auto_reset != 0)
-        return bad_arg("b747_eval_episodes: auto_reset must be 0 (an episode ends at its first done)");
-    if (params && b->obs_dim != 3 && b->obs_dim != 5)
-        return bad_arg("b747_eval_episodes: obs_dim (a policy runs with PID_LIKE 3 or SPEED_MODE 5 only; "
-                       "other observation types take params = NULL)");
-    if (!params && !b->action) return bad_arg("b747_eval_episodes: action is NULL (params = NULL holds b->action)");
-    if (n_env_steps == 0) return 0;
     const EvalArgs ea{params, n_env_steps, sig_row, scale, y_base, error_band, act_lo, act_hi, eval_out};
+    if (int32_t e = check_eval_args(nullptr, "b747_eval_episodes", *b, *cfg, c, ea)) return e;
+    if (n_env_steps == 0) return 0;
     const Consts C = consts_of(c);   // run-time constants: no instantiation of this kernel needs the DLL's defaults
     const int od = params ? b->obs_dim : 0;
     if (b->variant != B747_VARIANT_FAITHFUL) launch_eval_episodes_fast(*b, *cfg, C, ea, od, (hipStream_t)stream);
@@ -266,7 +349,7 @@ B747_API int32_t b747_policy_pack_batch(float *params, int32_t obs_dim, int32_t 
     if (!params) return bad_arg("b747_policy_pack_batch: params is NULL");
     if (obs_dim < 1 || obs_dim > 10) return bad_arg("b747_policy_pack_batch: obs_dim");
     if (n_policies < 0 || n_policies > 65535) return bad_arg("b747_policy_pack_batch: n_policies (0 .. 65535)");
-    if (policy_stride < policy_total_params(obs_dim) || policy_stride % 4 != 0)
+    if (!policy_stride_ok(policy_stride, obs_dim))
         return bad_arg("b747_policy_pack_batch: policy_stride (at least b747_policy_num_params floats, a multiple of 4)");
     if (n_policies == 0) return 0;
     hipLaunchKernelGGL(k_policy_pack_batch, dim3((policy_pack_threads(obs_dim) + 255) / 256, (unsigned)n_policies),
@@ -282,33 +365,16 @@ B747_API int32_t b747_eval_population(const b747_env_batch *b, const b747_env_co
 {
     int32_t r = check_env(b, cfg);
     if (r <= 0) return r;
-    if (!c) return bad_arg("b747_eval_population: consts is NULL");
-    if (!y_base || !eval_out) return bad_arg("b747_eval_population: y_base / eval_out is NULL");
-    if (n_env_steps < 0) return bad_arg("b747_eval_population: n_env_steps < 0");
-    if (sig_row < 0 || sig_row >= B747_NSIG) return bad_arg("b747_eval_population: sig_row (a B747_SIG_* row)");
-    if (!(act_lo <= act_hi)) return bad_arg("b747_eval_population: act_lo > act_hi");
-    if (!b->x_f64) return bad_arg("b747_eval_population: x_f64 (the episode kernel keeps fp64 state only)");
-    if (cfg->auto_reset != 0)
-        return bad_arg("b747_eval_population: auto_reset must be 0 (an episode ends at its first done)");
-    if (params && b->obs_dim != 3 && b->obs_dim != 5)
-        return bad_arg("b747_eval_population: obs_dim (a policy runs with PID_LIKE 3 or SPEED_MODE 5 only; "
-                       "other observation types take params = NULL)");
-    if (!params && !b->action) return bad_arg("b747_eval_population: action is NULL (params = NULL holds b->action)");
+    const char *const W = "b747_eval_population";
+    const EvalArgs ea{params, n_env_steps, sig_row, scale, y_base, error_band, act_lo, act_hi, eval_out};
+    if (int32_t e = check_eval_args(W, W, *b, *cfg, c, ea)) return e;
     if (params) {
-        if (envs_per_policy < 64 || envs_per_policy % 64 != 0)
-            return bad_arg("b747_eval_population: envs_per_policy (a positive multiple of 64: a wave flies one policy)");
-        if (n_policies < 1) return bad_arg("b747_eval_population: n_policies < 1 with params set");
-        if (b->n <= (int64_t)(n_policies - 1) * envs_per_policy || b->n > (int64_t)n_policies * envs_per_policy)
-            return bad_arg("b747_eval_population: n (outside ((n_policies - 1) * envs_per_policy, n_policies * "
-                           "envs_per_policy])");
-        if (policy_stride < policy_total_params(b->obs_dim) || policy_stride % 4 != 0)
-            return bad_arg("b747_eval_population: policy_stride (at least b747_policy_num_params floats and a multiple "
-                           "of 4: the fragments start on a 16-byte boundary)");
+        if (int32_t e = check_pop_groups(W, envs_per_policy, n_policies, "n_policies < 1 with params set")) return e;
+        if (int32_t e = check_pop_tiling(W, *b, n_policies, envs_per_policy, policy_stride)) return e;
     } else if (n_policies != 0) {
-        return bad_arg("b747_eval_population: n_policies must be 0 with params = NULL");
+        return bad_arg(W, "n_policies must be 0 with params = NULL");
     }
     if (n_env_steps == 0) return 0;
-    const EvalArgs ea{params, n_env_steps, sig_row, scale, y_base, error_band, act_lo, act_hi, eval_out};
     const PopArgs pa{policy_stride, params ? envs_per_policy / 64 : 1, pid_ss, pid_cs};
     const Consts C = consts_of(c);
     const int od = params ? b->obs_dim : 0;
@@ -326,35 +392,18 @@ B747_API int32_t b747_ppo_rollout_population(const b747_env_batch *b, const b747
 {
     int32_t r = check_env(b, cfg);
     if (r < 0) return r;
-    if (!c) return bad_arg("b747_ppo_rollout_population: consts is NULL");
-    if (!params) return bad_arg("b747_ppo_rollout_population: params is NULL");
-    if (!obs_buf) return bad_arg("b747_ppo_rollout_population: obs_buf is NULL");
-    if (!act_buf) return bad_arg("b747_ppo_rollout_population: act_buf is NULL");
-    if (!logp_buf) return bad_arg("b747_ppo_rollout_population: logp_buf is NULL");
-    if (!val_buf) return bad_arg("b747_ppo_rollout_population: val_buf is NULL");
-    if (!rew_buf) return bad_arg("b747_ppo_rollout_population: rew_buf is NULL");
-    if (!done_buf) return bad_arg("b747_ppo_rollout_population: done_buf is NULL");
-    if (T < 0) return bad_arg("b747_ppo_rollout_population: T < 0");
-    if (!(act_lo <= act_hi)) return bad_arg("b747_ppo_rollout_population: act_lo > act_hi");
-    if (envs_per_policy < 64 || envs_per_policy % 64 != 0)
-        return bad_arg("b747_ppo_rollout_population: envs_per_policy (a positive multiple of 64: a wave flies one policy)");
-    if (n_policies < 1) return bad_arg("b747_ppo_rollout_population: n_policies < 1");
-    if (r == 0) return bad_arg("b747_ppo_rollout_population: n (an empty batch holds no group)");
-    if (b->obs_dim != 3 && b->obs_dim != 5)
-        return bad_arg("b747_ppo_rollout_population: obs_dim (the one-wave rollout kernel runs a policy with PID_LIKE 3 or "
-                       "SPEED_MODE 5 only)");
-    if (!b->x_f64) return bad_arg("b747_ppo_rollout_population: x_f64 (the one-wave rollout kernel keeps fp64 state only)");
-    if (b->sig)
-        return bad_arg("b747_ppo_rollout_population: sig (no per-DLL-step signal recording inside the rollout kernel)");
-    if (b->n <= (int64_t)(n_policies - 1) * envs_per_policy || b->n > (int64_t)n_policies * envs_per_policy)
-        return bad_arg("b747_ppo_rollout_population: n (outside ((n_policies - 1) * envs_per_policy, n_policies * "
-                       "envs_per_policy])");
-    if (policy_stride < policy_total_params(b->obs_dim) || policy_stride % 4 != 0)
-        return bad_arg("b747_ppo_rollout_population: policy_stride (at least b747_policy_num_params floats and a multiple "
-                       "of 4: the fragments start on a 16-byte boundary)");
-    if (T == 0) return 0;
+    const char *const W = "b747_ppo_rollout_population";
     const RolloutLanesArgs ra{params, seed, step_base, T, act_lo, act_hi, obs_buf, act_buf, logp_buf, val_buf, rew_buf,
                               done_buf};
+    if (int32_t e = check_rollout_args(W, c, ra)) return e;
+    if (int32_t e = check_pop_groups(W, envs_per_policy, n_policies, "n_policies < 1")) return e;
+    if (r == 0) return bad_arg(W, "n (an empty batch holds no group)");
+    if (b->obs_dim != 3 && b->obs_dim != 5)
+        return bad_arg(W, "obs_dim (the one-wave rollout kernel runs a policy with PID_LIKE 3 or SPEED_MODE 5 only)");
+    if (!b->x_f64) return bad_arg(W, "x_f64 (the one-wave rollout kernel keeps fp64 state only)");
+    if (b->sig) return bad_arg(W, "sig (no per-DLL-step signal recording inside the rollout kernel)");
+    if (int32_t e = check_pop_tiling(W, *b, n_policies, envs_per_policy, policy_stride)) return e;
+    if (T == 0) return 0;
     const RolloutPopArgs pa{policy_stride, envs_per_policy / 64, rew_pop, last_val};
     const Consts C = consts_of(c);
     // (the launcher's second launch advances *step_base by T: ordered after the rollout kernel's last read of it)
@@ -375,34 +424,22 @@ B747_API int32_t b747_ppo_grad(const float *theta, int32_t obs_dim, const float 
                                int64_t batch, double clip_range, double ent_coef, double vf_coef, void *workspace,
                                float *grad, float *stats, void *stream)
 {
-    if (!theta) return bad_arg("theta is NULL");
-    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("obs_dim (3, 5, 7, 8 or 10)");
-    if (!obs) return bad_arg("obs is NULL");
-    if (!act) return bad_arg("act is NULL");
-    if (!old_logp) return bad_arg("old_logp is NULL");
-    if (!adv) return bad_arg("adv is NULL");
-    if (!ret) return bad_arg("ret is NULL");
-    if (!idx) return bad_arg("idx is NULL");
-    if (batch < 2) return bad_arg("batch < 2 (the advantages' standard deviation needs two rows)");
-    if (!workspace) return bad_arg("workspace is NULL");
-    if (!grad) return bad_arg("grad is NULL");
-    if (!stats) return bad_arg("stats is NULL");
-    return launched("b747_ppo_grad", launch_ppo_grad(theta, obs_dim, obs, act, old_logp, adv, ret, idx, batch, clip_range,
-                                                     ent_coef, vf_coef, workspace, grad, stats, (hipStream_t)stream));
+    const UpdData d{obs, act, old_logp, adv, ret};
+    if (int32_t e = check_upd_policy(nullptr, theta, obs_dim)) return e;
+    if (int32_t e = check_upd_rows(nullptr, d, idx, false, batch, 0, workspace)) return e;
+    if (int32_t e = check_not_null(nullptr, {{grad, "grad"}, {stats, "stats"}})) return e;
+    return launched("b747_ppo_grad", launch_ppo_grad(theta, obs_dim, d, idx, batch, {clip_range, ent_coef, vf_coef},
+                                                     workspace, grad, stats, (hipStream_t)stream));
 }
 
 B747_API int32_t b747_ppo_adam(float *theta, float *m, float *v, int64_t *t, const float *grad, int64_t n_params,
                                double grad_scale, double max_grad_norm, double lr, double beta1, double beta2,
                                double eps, void *stream)
 {
-    if (!theta) return bad_arg("theta is NULL");
-    if (!m) return bad_arg("m is NULL");
-    if (!v) return bad_arg("v is NULL");
-    if (!t) return bad_arg("t is NULL");
-    if (!grad) return bad_arg("grad is NULL");
+    if (int32_t e = check_not_null(nullptr, {{theta, "theta"}, {m, "m"}, {v, "v"}, {t, "t"}, {grad, "grad"}})) return e;
     if (n_params < 1) return bad_arg("n_params < 1");
-    return launched("b747_ppo_adam", launch_ppo_adam(theta, m, v, t, grad, n_params, grad_scale, max_grad_norm, lr, beta1,
-                                                     beta2, eps, (hipStream_t)stream));
+    return launched("b747_ppo_adam", launch_ppo_adam({theta, m, v, t}, grad, n_params, grad_scale,
+                                                     {max_grad_norm, beta1, beta2, eps}, lr, (hipStream_t)stream));
 }
 
 B747_API int32_t b747_ppo_gae(const float *rew, const float *val, const uint8_t *done, const float *last_value,
@@ -429,28 +466,13 @@ B747_API int32_t b747_ppo_epoch(float *theta, int32_t obs_dim, const float *obs,
                                 float *grad, float *m, float *v, int64_t *t, double max_grad_norm, double lr,
                                 double beta1, double beta2, double eps, float *stats, void *stream)
 {
-    if (!theta) return bad_arg("theta is NULL");
-    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("obs_dim (3, 5, 7, 8 or 10)");
-    if (!obs) return bad_arg("obs is NULL");
-    if (!act) return bad_arg("act is NULL");
-    if (!old_logp) return bad_arg("old_logp is NULL");
-    if (!adv) return bad_arg("adv is NULL");
-    if (!ret) return bad_arg("ret is NULL");
-    if (!perm) return bad_arg("perm is NULL");
-    if (n_rows < 2) return bad_arg("n_rows < 2 (the advantages' standard deviation needs two rows)");
-    if (batch_size < 2) return bad_arg("batch_size < 2 (the advantages' standard deviation needs two rows)");
-    if (n_rows % batch_size == 1)
-        return bad_arg("n_rows % batch_size == 1 (the last minibatch would be one row: no standard deviation)");
-    if (!workspace) return bad_arg("workspace is NULL");
-    if (!grad) return bad_arg("grad is NULL");
-    if (!m) return bad_arg("m is NULL");
-    if (!v) return bad_arg("v is NULL");
-    if (!t) return bad_arg("t is NULL");
-    if (!stats) return bad_arg("stats is NULL");
+    const UpdData d{obs, act, old_logp, adv, ret};
+    if (int32_t e = check_upd_policy(nullptr, theta, obs_dim)) return e;
+    if (int32_t e = check_upd_rows(nullptr, d, perm, true, n_rows, batch_size, workspace)) return e;
+    if (int32_t e = check_not_null(nullptr, {{grad, "grad"}, {m, "m"}, {v, "v"}, {t, "t"}, {stats, "stats"}})) return e;
     return launched("b747_ppo_epoch",
-                    launch_ppo_epoch(theta, obs_dim, obs, act, old_logp, adv, ret, perm, n_rows, batch_size, clip_range,
-                                     ent_coef, vf_coef, workspace, grad, m, v, t, max_grad_norm, lr, beta1, beta2, eps,
-                                     stats, (hipStream_t)stream));
+                    launch_ppo_epoch({theta, m, v, t}, obs_dim, d, perm, n_rows, batch_size, {clip_range, ent_coef, vf_coef},
+                                     workspace, grad, {max_grad_norm, beta1, beta2, eps}, lr, stats, (hipStream_t)stream));
 }
 
 B747_API int32_t b747_ppo_epoch_population(float *theta, int32_t n_policies, int64_t policy_stride, int32_t obs_dim,
@@ -461,44 +483,17 @@ B747_API int32_t b747_ppo_epoch_population(float *theta, int32_t n_policies, int
                                            const double *lr, double beta1, double beta2, double eps, float *stats,
                                            void *stream)
 {
-    if (!theta) return bad_arg("b747_ppo_epoch_population: theta is NULL");
-    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("b747_ppo_epoch_population: obs_dim (3, 5, 7, 8 or 10)");
-    if (n_policies < 1) return bad_arg("b747_ppo_epoch_population: n_policies < 1");
-    if (policy_stride < policy_total_params(obs_dim) || policy_stride % 4 != 0)
-        return bad_arg("b747_ppo_epoch_population: policy_stride (at least b747_policy_num_params floats and a multiple "
-                       "of 4)");
-    if (!obs) return bad_arg("b747_ppo_epoch_population: obs is NULL");
-    if (!act) return bad_arg("b747_ppo_epoch_population: act is NULL");
-    if (!old_logp) return bad_arg("b747_ppo_epoch_population: old_logp is NULL");
-    if (!adv) return bad_arg("b747_ppo_epoch_population: adv is NULL");
-    if (!ret) return bad_arg("b747_ppo_epoch_population: ret is NULL");
-    if (!perm) return bad_arg("b747_ppo_epoch_population: perm is NULL");
-    if (n_rows < 2)
-        return bad_arg("b747_ppo_epoch_population: n_rows < 2 (the advantages' standard deviation needs two rows)");
-    if (batch_size < 2)
-        return bad_arg("b747_ppo_epoch_population: batch_size < 2 (the advantages' standard deviation needs two rows)");
-    if (n_rows % batch_size == 1)
-        return bad_arg("b747_ppo_epoch_population: n_rows % batch_size == 1 (the last minibatch would be one row: no "
-                       "standard deviation)");
-    if (!workspace) return bad_arg("b747_ppo_epoch_population: workspace is NULL");
-    if (!grad) return bad_arg("b747_ppo_epoch_population: grad is NULL");
-    if (!m) return bad_arg("b747_ppo_epoch_population: m is NULL");
-    if (!v) return bad_arg("b747_ppo_epoch_population: v is NULL");
-    if (!t) return bad_arg("b747_ppo_epoch_population: t is NULL");
-    if (!lr) return bad_arg("b747_ppo_epoch_population: lr is NULL (a host array, one learning rate per member)");
-    if (!stats) return bad_arg("b747_ppo_epoch_population: stats is NULL");
-    // member p: b747_ppo_epoch's launches on its own parameters, moments, step count, sample order and statistics
-    // rows; the rollout buffers, the gradient and the workspace are shared (the stream orders the members)
-    const int64_t n_params = PolicyLayout::of(obs_dim).total, n_mb = (n_rows + batch_size - 1) / batch_size;
-    for (int32_t p = 0; p < n_policies; ++p) {
-        const hipError_t e = launch_ppo_epoch(theta + p * policy_stride, obs_dim, obs, act, old_logp, adv, ret,
-                                              perm + p * n_rows, n_rows, batch_size, clip_range, ent_coef, vf_coef,
-                                              workspace, grad, m + p * n_params, v + p * n_params, t + p, max_grad_norm,
-                                              lr[p], beta1, beta2, eps, stats + p * n_mb * kUpdStats,
-                                              (hipStream_t)stream);
-        if (e != hipSuccess) return fail(e, "b747_ppo_epoch_population");
-    }
-    return 0;
+    const char *const W = "b747_ppo_epoch_population";
+    const UpdData d{obs, act, old_logp, adv, ret};
+    if (int32_t e = check_upd_policy(W, theta, obs_dim)) return e;
+    if (int32_t e = check_upd_members(W, n_policies, policy_stride, obs_dim)) return e;
+    if (int32_t e = check_upd_rows(W, d, perm, true, n_rows, batch_size, workspace)) return e;
+    if (int32_t e = check_not_null(W, {{grad, "grad"}, {m, "m"}, {v, "v"}, {t, "t"}})) return e;
+    if (!lr) return bad_arg(W, "lr is NULL (a host array, one learning rate per member)");
+    if (!stats) return bad_arg(W, "stats is NULL");
+    return launched(W, launch_ppo_epoch_population({theta, m, v, t}, n_policies, policy_stride, obs_dim, d, perm, n_rows,
+                                                   batch_size, {clip_range, ent_coef, vf_coef}, workspace, grad,
+                                                   {max_grad_norm, beta1, beta2, eps}, lr, stats, (hipStream_t)stream));
 }
 
 B747_API int64_t b747_ppo_epoch_batched_workspace(int32_t obs_dim, int64_t batch_size)
@@ -518,39 +513,19 @@ B747_API int32_t b747_ppo_epoch_batched(float *theta, int32_t n_policies, int64_
                                         const double *lr_dev, double beta1, double beta2, double eps, float *stats,
                                         void *stream)
 {
-    if (!theta) return bad_arg("b747_ppo_epoch_batched: theta is NULL");
-    if (!policy_obs_dim_ok(obs_dim)) return bad_arg("b747_ppo_epoch_batched: obs_dim (3, 5, 7, 8 or 10)");
-    if (n_policies < 1) return bad_arg("b747_ppo_epoch_batched: n_policies < 1");
-    if (policy_stride < policy_total_params(obs_dim) || policy_stride % 4 != 0)
-        return bad_arg("b747_ppo_epoch_batched: policy_stride (at least b747_policy_num_params floats and a multiple "
-                       "of 4)");
-    if (!obs) return bad_arg("b747_ppo_epoch_batched: obs is NULL");
-    if (!act) return bad_arg("b747_ppo_epoch_batched: act is NULL");
-    if (!old_logp) return bad_arg("b747_ppo_epoch_batched: old_logp is NULL");
-    if (!adv) return bad_arg("b747_ppo_epoch_batched: adv is NULL");
-    if (!ret) return bad_arg("b747_ppo_epoch_batched: ret is NULL");
-    if (!perm) return bad_arg("b747_ppo_epoch_batched: perm is NULL");
-    if (n_rows < 2)
-        return bad_arg("b747_ppo_epoch_batched: n_rows < 2 (the advantages' standard deviation needs two rows)");
-    if (batch_size < 2)
-        return bad_arg("b747_ppo_epoch_batched: batch_size < 2 (the advantages' standard deviation needs two rows)");
-    if (n_rows % batch_size == 1)
-        return bad_arg("b747_ppo_epoch_batched: n_rows % batch_size == 1 (the last minibatch would be one row: no "
-                       "standard deviation)");
-    if (!workspace) return bad_arg("b747_ppo_epoch_batched: workspace is NULL");
+    const char *const W = "b747_ppo_epoch_batched";
+    const UpdData d{obs, act, old_logp, adv, ret};
+    if (int32_t e = check_upd_policy(W, theta, obs_dim)) return e;
+    if (int32_t e = check_upd_members(W, n_policies, policy_stride, obs_dim)) return e;
+    if (int32_t e = check_upd_rows(W, d, perm, true, n_rows, batch_size, workspace)) return e;
     if (workspace_bytes < upd_pop_ws_bytes(obs_dim, batch_size))
-        return bad_arg("b747_ppo_epoch_batched: workspace_bytes (below one member's "
-                       "b747_ppo_epoch_batched_workspace(obs_dim, batch_size))");
-    if (!m) return bad_arg("b747_ppo_epoch_batched: m is NULL");
-    if (!v) return bad_arg("b747_ppo_epoch_batched: v is NULL");
-    if (!t) return bad_arg("b747_ppo_epoch_batched: t is NULL");
-    if (!lr_dev) return bad_arg("b747_ppo_epoch_batched: lr_dev is NULL (a device array, one learning rate per member)");
-    if (!stats) return bad_arg("b747_ppo_epoch_batched: stats is NULL");
-    return launched("b747_ppo_epoch_batched",
-                    launch_ppo_epoch_batched(theta, n_policies, policy_stride, obs_dim, obs, act, old_logp, adv, ret, perm,
-                                             n_rows, batch_size, clip_range, ent_coef, vf_coef, workspace,
-                                             workspace_bytes, m, v, t, max_grad_norm, lr_dev, beta1, beta2, eps, stats,
-                                             (hipStream_t)stream));
+        return bad_arg(W, "workspace_bytes (below one member's b747_ppo_epoch_batched_workspace(obs_dim, batch_size))");
+    if (int32_t e = check_not_null(W, {{m, "m"}, {v, "v"}, {t, "t"}})) return e;
+    if (!lr_dev) return bad_arg(W, "lr_dev is NULL (a device array, one learning rate per member)");
+    if (!stats) return bad_arg(W, "stats is NULL");
+    return launched(W, launch_ppo_epoch_batched({theta, m, v, t}, n_policies, policy_stride, obs_dim, d, perm, n_rows,
+                                                batch_size, {clip_range, ent_coef, vf_coef}, workspace, workspace_bytes,
+                                                {max_grad_norm, beta1, beta2, eps}, lr_dev, stats, (hipStream_t)stream));
 }
 
 B747_API int32_t b747_consts_default(b747_consts *c)

@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "b747_dynamics.h"
 #include "b747_env.h"
 #include "b747_policy.h"   // PolicyLayout (flat_params order), PH
@@ -48,16 +50,18 @@ B747_HD constexpr int64_t upd_ws_bytes(int od)
     return upd_ws_grad() + (int64_t)sizeof(float) * PolicyLayout::of(od).total * kUpdMaxWG;
 }
 
-// The member-batched update (b747_ppo_epoch_batched).  Workgroups of k_ppo_grad for a minibatch of
-// `batch` rows: two tiles in flight per workgroup and net, at most one workgroup per CU
+// Workgroups of k_ppo_grad / k_pop_grad for a minibatch of `batch` rows (every launcher's grid): two tiles in flight
+// per workgroup and net, at most one workgroup per CU
 B747_HD constexpr int upd_n_wg(int64_t batch)
 {
     const int64_t tiles = (batch + kUpdTile - 1) / kUpdTile, want = (tiles + 1) / 2;
     return (int)(want < kUpdMaxWG ? want : kUpdMaxWG);
 }
-// One member's slice of its workspace (bytes): [adv partials: double 2 x kUpdAdvBlocks][sum partials: double kUpdSums
-// x n_wg][gradient partials: float P x n_wg][the gradient: float P], n_wg = upd_n_wg(batch_size); the slice length
-// is rounded up to 16 bytes
+static_assert(upd_n_wg(2) == 1 && upd_n_wg(64) == 1 && upd_n_wg(65) == 2, "one workgroup per two tiles");
+static_assert(upd_n_wg(16320) == 255 && upd_n_wg(16321) == 256 && upd_n_wg(40000) == 256, "at most kUpdMaxWG");
+// The member-batched update (b747_ppo_epoch_batched).  One member's slice of its workspace (bytes):
+// [adv partials: double 2 x kUpdAdvBlocks][sum partials: double kUpdSums x n_wg][gradient partials: float P x n_wg]
+// [the gradient: float P], n_wg = upd_n_wg(batch_size); the slice length is rounded up to 16 bytes
 B747_HD constexpr int64_t upd_pop_ws_grad(int64_t batch_size)
 {
     return upd_ws_sums() + (int64_t)sizeof(double) * kUpdSums * upd_n_wg(batch_size);
@@ -81,33 +85,67 @@ struct UpdPopArgs {
     int64_t stats_stride;    // floats: the statistics rows of one epoch
 };
 
-// Launchers, defined in b747_ppo_update.hip (hidden: not part of the C ABI).  Arguments are validated by the caller.
-__attribute__((visibility("hidden"))) hipError_t launch_ppo_grad(const float *theta, int od, const float *obs,
-                                                                 const float *act, const float *old_logp,
-                                                                 const float *adv, const float *ret, const int64_t *idx,
-                                                                 int64_t batch, double clip_range, double ent_coef,
-                                                                 double vf_coef, void *workspace, float *grad,
-                                                                 float *stats, hipStream_t s);
-__attribute__((visibility("hidden"))) hipError_t launch_ppo_adam(float *theta, float *m, float *v, int64_t *t,
-                                                                 const float *grad, int64_t n_params, double grad_scale,
-                                                                 double max_grad_norm, double lr, double beta1,
-                                                                 double beta2, double eps, hipStream_t s);
+// The obs_dims a policy kernel is instantiated for, written once: with_obs_dim(od, otherwise, f) returns
+// f(std::integral_constant<int, od>{}), or `otherwise` for an od not in the list -- every instantiation of f is
+// compiled, one is run (as with_bools)
+template <int OD>
+using obs_dim_c = std::integral_constant<int, OD>;
+template <class R, class F>
+R with_obs_dim(int od, R otherwise, F &&f)
+{
+    auto among = [&](auto... c) { return ((od == c() && (otherwise = f(c), true)) || ...); };
+    // PID_LIKE, SPEED_MODE, MODEL_STATE, PID_AERO, PID_SPEED_AERO
+    among(obs_dim_c<3>{}, obs_dim_c<5>{}, obs_dim_c<7>{}, obs_dim_c<8>{}, obs_dim_c<10>{});
+    return otherwise;
+}
+inline bool policy_obs_dim_ok(int od) { return with_obs_dim(od, false, [](auto) { return true; }); }
+
+// What the launchers take, by name.  The rollout buffers an update reads (rows of T x N, indexed through idx / perm):
+struct UpdData {
+    const float *obs, *act, *old_logp, *adv, *ret;
+};
+struct UpdLoss {
+    double clip_range, ent_coef, vf_coef;
+};
+// (the learning rate is not here: a scalar, a host array or a device array, as the entry point has it)
+struct UpdAdam {
+    double max_grad_norm, beta1, beta2, eps;
+};
+// One member's optimiser state: the parameters, Adam's moments and step count
+struct UpdState {
+    float *theta, *m, *v;
+    int64_t *t;
+};
+
+// Launchers, defined in b747_ppo_update.hip (hidden: not part of the C ABI).  Arguments are validated by the caller;
+// an obs_dim without kernels (with_obs_dim) gives hipErrorInvalidValue.
+#define B747_HIDDEN __attribute__((visibility("hidden")))
+B747_HIDDEN hipError_t launch_ppo_grad(const float *theta, int od, const UpdData &d, const int64_t *idx, int64_t batch,
+                                       const UpdLoss &loss, void *workspace, float *grad, float *stats, hipStream_t s);
+B747_HIDDEN hipError_t launch_ppo_adam(const UpdState &st, const float *grad, int64_t n_params, double grad_scale,
+                                       const UpdAdam &adam, double lr, hipStream_t s);
 // Every minibatch of one epoch (b747_ppo_epoch): launch_ppo_grad's launches on perm + j batch_size, then launch_ppo_adam
 // with grad_scale 1, for j = 0 .. ceil(n_rows / batch_size) - 1; the first launch error ends the loop and is returned
-__attribute__((visibility("hidden"))) hipError_t launch_ppo_epoch(
-    float *theta, int od, const float *obs, const float *act, const float *old_logp, const float *adv, const float *ret,
-    const int64_t *perm, int64_t n_rows, int64_t batch_size, double clip_range, double ent_coef, double vf_coef,
-    void *workspace, float *grad, float *m, float *v, int64_t *t, double max_grad_norm, double lr, double beta1,
-    double beta2, double eps, float *stats, hipStream_t s);
+B747_HIDDEN hipError_t launch_ppo_epoch(const UpdState &st, int od, const UpdData &d, const int64_t *perm, int64_t n_rows,
+                                        int64_t batch_size, const UpdLoss &loss, void *workspace, float *grad,
+                                        const UpdAdam &adam, double lr, float *stats, hipStream_t s);
+// launch_ppo_epoch for member p = 0 .. n_policies - 1 in turn (b747_ppo_epoch_population): its own parameters (st is
+// member 0's, theta policy_stride floats apart), moments, step count, sample order, statistics rows and lr[p] (a host
+// array); the rollout buffers, the gradient and the workspace are shared (the stream orders the members)
+B747_HIDDEN hipError_t launch_ppo_epoch_population(const UpdState &st, int n_policies, int64_t policy_stride, int od,
+                                                   const UpdData &d, const int64_t *perm, int64_t n_rows,
+                                                   int64_t batch_size, const UpdLoss &loss, void *workspace,
+                                                   float *grad, const UpdAdam &adam, const double *lr, float *stats,
+                                                   hipStream_t s);
 // One epoch of n_policies members, four launches per minibatch for a whole chunk of members (b747_ppo_epoch_batched):
 // chunks of min(n_policies, workspace_bytes / upd_pop_ws_bytes, kUpdPopMaxMembers) members, each through all its
 // minibatches before the next; lr is a device array; the first launch error ends the loops and is returned
-__attribute__((visibility("hidden"))) hipError_t launch_ppo_epoch_batched(
-    float *theta, int n_policies, int64_t policy_stride, int od, const float *obs, const float *act,
-    const float *old_logp, const float *adv, const float *ret, const int64_t *perm, int64_t n_rows, int64_t batch_size,
-    double clip_range, double ent_coef, double vf_coef, void *workspace, int64_t workspace_bytes, float *m, float *v,
-    int64_t *t, double max_grad_norm, const double *lr, double beta1, double beta2, double eps, float *stats,
-    hipStream_t s);
+B747_HIDDEN hipError_t launch_ppo_epoch_batched(const UpdState &st, int n_policies, int64_t policy_stride, int od,
+                                                const UpdData &d, const int64_t *perm, int64_t n_rows,
+                                                int64_t batch_size, const UpdLoss &loss, void *workspace,
+                                                int64_t workspace_bytes, const UpdAdam &adam, const double *lr,
+                                                float *stats, hipStream_t s);
+#undef B747_HIDDEN
 
 #ifndef B747_PPO_UPDATE_NO_KERNELS
 

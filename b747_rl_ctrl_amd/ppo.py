@@ -144,6 +144,40 @@ def allreduce_gradients(params, group=None):
         off += g.numel()
 
 
+_p = torch.Tensor.data_ptr      # a tensor's address, as the C ABI takes it
+
+
+def load_flat(net: ActorCritic, vec: torch.Tensor):
+    """Copy the leading entries of the flat vector `vec` (flat_param_list order) into net's parameters"""
+    with torch.no_grad():
+        off = 0
+        for prm in net.flat_param_list():
+            prm.copy_(vec[off:off + prm.numel()].view_as(prm))
+            off += prm.numel()
+
+
+def _rollout_buffers(T: int, n: int, od: int, dev):
+    """The time-major rollout of T steps of n envs: obs, act, logp, val, rew, done, adv, ret (zeros on dev)"""
+    z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)
+    return z(T, n, od), z(T, n, 1), z(T, n), z(T, n), z(T, n), z(T, n, dt=torch.bool), z(T, n), z(T, n)
+
+
+def _step_test_kwargs(env: BatchControllerEnv) -> dict:
+    """The settings of a step-response test env that flies what `env` trains (evaluate.run_step_tests' keywords)"""
+    return dict(observation_type=env.observation_type, reward_type=env.reward_type, ctrl_mode=env.ctrl_mode,
+                norm_obs=env.norm_obs, norm_act=env.norm_act, sample_time=env.sample_time, device=env.device,
+                action_max=env.action_max, vartheta_max=env.vartheta_max, use_limiter=env.use_limiter,
+                variant={0: "fast", 1: "faithful", 2: "mixed"}[env.variant])
+
+
+def _train_log(mean, last, loss, explained_variance, std) -> dict:
+    """train()'s log values by name.  mean: the eight statistics columns averaged over every minibatch; last: approx_kl
+    and kl_term_scale, the last epoch's means of columns 4 and 6 -- scalars (PPO) or [P] tensors (PopulationPPO)"""
+    return {"entropy_loss": mean[2], "policy_gradient_loss": mean[0], "value_loss": mean[1], "approx_kl": last[0],
+            "clip_fraction": mean[3], "loss": loss, "explained_variance": explained_variance, "std": std,
+            "pg_term_scale": mean[5], "kl_term_scale": last[1], "policy_loss": mean[0]}
+
+
 @dataclass
 class PPOConfig:
     n_steps: int = 2048
@@ -211,10 +245,8 @@ class PPO:
         lo, hi = env.action_space.low, env.action_space.high
         self.act_lo, self.act_hi = float(lo), float(hi)
         z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)
-        self.obs_buf, self.act_buf = z(T, n, od), z(T, n, 1)
-        self.logp_buf, self.val_buf, self.rew_buf = z(T, n), z(T, n), z(T, n)
-        self.done_buf = z(T, n, dt=torch.bool)
-        self.adv_buf, self.ret_buf = z(T, n), z(T, n)
+        (self.obs_buf, self.act_buf, self.logp_buf, self.val_buf, self.rew_buf, self.done_buf, self.adv_buf,
+         self.ret_buf) = _rollout_buffers(T, n, od, dev)
         self.last_obs = z(n, od)
         self._last_obs_from_env = False   # (rollout kernel: last_obs is env.obs, copied when compute_gae reads it)
         self.last_done = z(n, dt=torch.bool)
@@ -294,7 +326,7 @@ class PPO:
         row + the env's action buffer; the env step writes reward / done straight into the
         rollout buffers (b747_env_rollout with K = 1).  noise [n] fp32 on the device (optional): the
         kernel's standard normal draws instead of its Philox ones (b747_policy_act's noise argument)."""
-        env, p = self.env, lambda x: x.data_ptr()
+        env, p = self.env, _p
         stream = torch.cuda.current_stream().cuda_stream
         if noise is not None:
             assert noise.dtype == torch.float32 and noise.is_contiguous() and noise.numel() == env.n \
@@ -309,7 +341,7 @@ class PPO:
     def _ppo_rollout(self, T: int) -> int:
         """The rollout kernel's call (b747_ppo_rollout, or b747_ppo_rollout_lanes for rollout_kernel="lanes": the same
         arguments); the library's return code."""
-        env, p = self.env, lambda x: x.data_ptr()
+        env, p = self.env, _p
         b = env._batch()
         call = self._L.b747_ppo_rollout
         if self.rollout_kernel == "lanes":
@@ -402,7 +434,7 @@ class PPO:
         c = self.cfg
         _, last_value = self.policy(self._bootstrap_obs())
         if self.gae_kernel:
-            p, last_value = (lambda x: x.data_ptr()), last_value.contiguous()
+            p, last_value = _p, last_value.contiguous()
             self._lib.check(self._L.b747_ppo_gae(
                 p(self.rew_buf), p(self.val_buf), p(self.done_buf), p(last_value), T, self.env.n, c.gamma, c.gae_lambda,
                 p(self.adv_buf), p(self.ret_buf), torch.cuda.current_stream().cuda_stream), "b747_ppo_gae")
@@ -457,24 +489,16 @@ class PPO:
                     rows[k].copy_(st)
                 k += 1
         if self.fused_update:       # the flat vector is the master copy during the epochs: hand it to the modules
-            with torch.no_grad():
-                off = 0
-                for prm in self.policy.flat_param_list():
-                    prm.copy_(self.flat[off:off + prm.numel()].view_as(prm))
-                    off += prm.numel()
+            load_flat(self.policy, self.flat)
         self.sync_params()
         with torch.no_grad():
             v, r = self.val_buf[:T].reshape(N), views[4]
             var_r = r.var(unbiased=False)
             ev = 1 - (r - v).var(unbiased=False) / var_r if float(var_r) != 0 else torch.tensor(float("nan"))
             mean = rows.double().mean(0).tolist()
-            stats = {"entropy_loss": mean[2], "policy_gradient_loss": mean[0], "value_loss": mean[1],
-                     "approx_kl": float(rows[(c.n_epochs - 1) * n_mb:, 4].double().mean()), "clip_fraction": mean[3],
-                     "loss": float(loss) if loss is not None else float("nan"),
-                     "explained_variance": float(ev), "std": float(self.policy.log_std.exp().mean()),
-                     "pg_term_scale": mean[5], "kl_term_scale": float(rows[(c.n_epochs - 1) * n_mb:, 6].double().mean())}
-        stats["policy_loss"] = stats["policy_gradient_loss"]
-        return stats
+            last = [float(rows[(c.n_epochs - 1) * n_mb:, k].double().mean()) for k in (4, 6)]
+            return _train_log(mean, last, float(loss) if loss is not None else float("nan"), float(ev),
+                              float(self.policy.log_std.exp().mean()))
 
     def _minibatch(self, idx, views):
         """One clipped-surrogate step on the rows `idx` of the rollout views -> (loss, [pg, vf, entropy loss,
@@ -508,7 +532,7 @@ class PPO:
         synchronisation): b747_ppo_grad gathers the rows `idx` from the time-major rollout buffers and writes the
         gradient and the statistics row [.., loss]; b747_ppo_adam clips and steps.  Data-parallel: one all-reduce of
         the flat gradient between them, its 1 / world folded into the Adam call.  Returns the loss (a view of row)."""
-        c, p = self.cfg, lambda x: x.data_ptr()
+        c, p = self.cfg, _p
         idx = idx.to(torch.int64).contiguous()
         stream = torch.cuda.current_stream().cuda_stream
         assert idx.numel() >= 2, "a minibatch of one row has no advantage standard deviation"
@@ -529,7 +553,7 @@ class PPO:
         """The minibatch loop of one epoch over the sample order `perm` as one b747_ppo_epoch call: per minibatch the
         launches of _minibatch_fused, from a C loop (single rank).  rows [n_mb][8] receives the statistics.  Returns
         the last minibatch's loss (a view of rows)."""
-        c, p = self.cfg, lambda x: x.data_ptr()
+        c, p = self.cfg, _p
         perm = perm.to(torch.int64).contiguous()
         assert perm.numel() == N, "minibatch_order must give every row of the rollout once"
         self._lib.check(self._L.b747_ppo_epoch(
@@ -557,15 +581,8 @@ class PPO:
         loop can call it between rollouts without leaving the device.  Returns run_step_tests' metrics."""
         from .evaluate import run_step_tests_fused
         e = self.env
-        if self.fused:
-            policy = self                     # the packed buffer the rollout kernels read (self.flat)
-        else:
-            policy = self.policy
-        kw = dict(observation_type=e.observation_type, reward_type=e.reward_type, ctrl_mode=e.ctrl_mode,
-                  norm_obs=e.norm_obs, norm_act=e.norm_act, sample_time=e.sample_time, device=e.device,
-                  action_max=e.action_max, vartheta_max=e.vartheta_max, use_limiter=e.use_limiter,
-                  variant={0: "fast", 1: "faithful", 2: "mixed"}[e.variant])
-        kw.update(kwargs)
+        policy = self if self.fused else self.policy      # self: the packed buffer the rollout kernels read (self.flat)
+        kw = _step_test_kwargs(e) | kwargs
         return run_step_tests_fused(policy, vartheta_ref, state0=state0, tk=e.tk if tk is None else tk, **kw)
 
 
@@ -639,10 +656,8 @@ class PopulationPPO:
             self.lr_dev = torch.tensor(lrs, dtype=torch.float64, device=dev)      # b747_ppo_epoch_batched reads them there
             self.upd_ws_batched = torch.empty(max(1, min(P, self.BATCHED_WORKSPACE_CAP // per)) * per, dtype=torch.uint8,
                                               device=dev)
-        self.obs_buf, self.act_buf = z(T, n, od), z(T, n, 1)
-        self.logp_buf, self.val_buf, self.rew_buf = z(T, n), z(T, n), z(T, n)
-        self.done_buf = z(T, n, dt=torch.bool)
-        self.adv_buf, self.ret_buf = z(T, n), z(T, n)
+        (self.obs_buf, self.act_buf, self.logp_buf, self.val_buf, self.rew_buf, self.done_buf, self.adv_buf,
+         self.ret_buf) = _rollout_buffers(T, n, od, dev)
         self.last_val = z(n)
         self.step_base = torch.zeros(1, dtype=torch.int64, device=dev)
         self.act_lo, self.act_hi = float(env.action_space.low), float(env.action_space.high)
@@ -668,7 +683,7 @@ class PopulationPPO:
     def compute_gae(self, T: Optional[int] = None):
         """PPO.compute_gae for every member: one b747_ppo_gae launch over all N envs, bootstrapped with the rollout
         kernel's last_val"""
-        T, c, p = T or self.cfg.n_steps, self.cfg, lambda x: x.data_ptr()
+        T, c, p = T or self.cfg.n_steps, self.cfg, _p
         self._lib.check(self._L.b747_ppo_gae(
             p(self.rew_buf), p(self.val_buf), p(self.done_buf), p(self.last_val), T, self.env.n, c.gamma, c.gae_lambda,
             p(self.adv_buf), p(self.ret_buf), torch.cuda.current_stream().cuda_stream), "b747_ppo_gae")
@@ -694,7 +709,7 @@ class PopulationPPO:
         T, c, P, epp = T or self.cfg.n_steps, self.cfg, self.n_members, self.envs_per_member
         if self.env.n != P * epp:
             raise ValueError("PopulationPPO.train: every member needs envs_per_member envs (one n_rows for all members)")
-        dev, n_rows, p = self.env.device, T * epp, lambda x: x.data_ptr()
+        dev, n_rows, p = self.env.device, T * epp, _p
         n_mb = -(-n_rows // c.batch_size)
         rows_of = self.member_rows(T)
         stats = torch.empty(c.n_epochs, P, n_mb, 8, dtype=torch.float32, device=dev)
@@ -726,12 +741,8 @@ class PopulationPPO:
         r = self.ret_buf[:T].reshape(T, P, epp).permute(1, 0, 2).reshape(P, -1)
         var_r = r.var(dim=1, unbiased=False)
         ev = torch.where(var_r != 0, 1 - (r - v).var(dim=1, unbiased=False) / var_r, torch.full_like(var_r, float("nan")))
-        out = {"entropy_loss": mean[:, 2], "policy_gradient_loss": mean[:, 0], "value_loss": mean[:, 1],
-               "approx_kl": last[:, 4], "clip_fraction": mean[:, 3], "loss": st[-1, :, -1, 7],
-               "explained_variance": ev, "std": self.flat[:, self.n_params - 1].exp(),
-               "pg_term_scale": mean[:, 5], "kl_term_scale": last[:, 6]}
-        out["policy_loss"] = out["policy_gradient_loss"]
-        return out
+        return _train_log(mean.unbind(1), (last[:, 4], last[:, 6]), st[-1, :, -1, 7], ev,
+                          self.flat[:, self.n_params - 1].exp())
 
     def repack(self):
         """Derive the packed sections of every member from its flat parameters (after an update): one launch"""
@@ -753,11 +764,7 @@ class PopulationPPO:
     def member(self, p: int) -> ActorCritic:
         """A copy of member p's policy as an ActorCritic on the env's device"""
         net = ActorCritic(self.env.obs_dim).to(self.env.device)
-        with torch.no_grad():
-            off = 0
-            for prm in net.flat_param_list():
-                prm.copy_(self.flat[p, off:off + prm.numel()].view_as(prm))
-                off += prm.numel()
+        load_flat(net, self.flat[p])
         return net
 
     def step_tests(self, vartheta_ref, state0=(0, 11000, 250, 0, 0, 0), tk: Optional[float] = None, **kwargs):
@@ -766,9 +773,5 @@ class PopulationPPO:
         "mean_settling_time" as [P] and "best", the member optimize() would keep."""
         from .evaluate import population_step_tests
         e = self.env
-        kw = dict(observation_type=e.observation_type, reward_type=e.reward_type, ctrl_mode=e.ctrl_mode,
-                  norm_obs=e.norm_obs, norm_act=e.norm_act, sample_time=e.sample_time, device=e.device,
-                  action_max=e.action_max, vartheta_max=e.vartheta_max, use_limiter=e.use_limiter,
-                  variant={0: "fast", 1: "faithful", 2: "mixed"}[e.variant])
-        kw.update(kwargs)
+        kw = _step_test_kwargs(e) | kwargs
         return population_step_tests(self.flat, vartheta_ref, state0=state0, tk=e.tk if tk is None else tk, **kw)
