@@ -8,7 +8,12 @@
 // env, the small layers on the VALU from an LDS copy of the parameters, activations in registers,
 // and the two 64x64 hidden layers on the matrix cores as v_mfma_f32_32x32x16_f16 with an f16
 // hi/lo split of both operands (x = hi + lo; hi*hi + hi*lo + lo*hi accumulated in f32 keeps ~22
-// significant bits -- within 2e-5 of the f32 torch policy, tests/test_gpu_ppo.py).  The f16
+// significant bits -- against the float64 policy, mean and value stay within 16 times the error of
+// the f32 torch policy plus 2^-22 of the output's scale, from initialisation scale to weights ten
+// times that with saturated tanh units and observations from 1e-3 to beyond the f16 range:
+// measured per kernel form in DESIGN.md "Policy forward against float64", held by
+// tests/test_gpu_policy_forward_f64.py; tests/test_policy_forward_model.py restates the arithmetic
+// on the CPU and shows that a dropped lo*hi product or flushed f16 subnormals miss that bar).  The f16
 // MFMAs take 1/5 of the f32-MFMA time and, unlike them, run beside the VALU.  The second hidden
 // layer is never materialised (folded straight into the 64->1 head).  tanh is 1 - 2/(2^(2x/ln2)+1)
 // on the hardware exp2/rcp, with its scale and affine part folded into derived parameters.

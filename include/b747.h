@@ -301,7 +301,9 @@ int32_t b747_env_kernel(const b747_env_batch *b, const b747_env_config *cfg, con
  * derived parameters with tanh's scale and affine part folded in, and (from a 16-byte boundary) 1024
  * floats of layer-1 matrix-core fragments (obs_dim <= 4: the first layer of both heads as one
  * v_mfma_f32_32x32x16_f16 per 32-unit tile, its f16 hi/lo split and bias folded into K) -- call it after
- * every parameter update; b747_policy_num_params counts all four parts.  Outputs agree with the f32 torch policy within 2e-5 (f16 hi/lo split products, tests/test_gpu_ppo.py). */
+ * every parameter update; b747_policy_num_params counts all four parts.  Outputs agree with the float64 policy
+ * within 16 times the f32 torch policy's own error plus 2^-22 of the output's scale (f16 hi/lo split products;
+ * DESIGN.md "Policy forward against float64", tests/test_gpu_policy_forward_f64.py). */
 int32_t b747_policy_num_params(int32_t obs_dim);
 /* T rollout steps (policy forward + sample + clip + env step, as b747_policy_act followed by
  * b747_env_step with the same Philox noise) for every env in ONE launch -- each env on two waves, the policy
