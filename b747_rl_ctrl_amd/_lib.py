@@ -104,6 +104,12 @@ SIGNATURES = {
     "b747_ppo_epoch_batched_workspace": ([_I32, _I64], _I64),
     "b747_ppo_epoch_batched": ([_V, _I32, _I64, _I32] + [_V] * 6 + [_I64, _I64, _F64, _F64, _F64, _V, _I64] + [_V] * 3
                                + [_F64, _V, _F64, _F64, _F64, _V, _V], _I32),
+    # (per-member hyper-parameter tables, [n_policies][8] doubles: a device table, a host table, a device table)
+    "b747_ppo_gae_population": ([_V, _V, _V, _V, _I32, _I64, _I32, _I32, _V, _V, _V, _V], _I32),
+    "b747_ppo_epoch_population_hyper": ([_V, _I32, _I64, _I32] + [_V] * 6 + [_I64, _I64, _V] + [_V] * 5
+                                        + [_F64, _F64, _F64, _V, _V], _I32),
+    "b747_ppo_epoch_batched_hyper": ([_V, _I32, _I64, _I32] + [_V] * 6 + [_I64, _I64, _V, _V, _I64] + [_V] * 3
+                                     + [_F64, _F64, _F64, _V, _V], _I32),
 }
 
 

@@ -460,6 +460,28 @@ B747_API int32_t b747_ppo_gae(const float *rew, const float *val, const uint8_t 
                     launch_ppo_gae(rew, val, done, last_value, T, N, gamma, gae_lambda, adv, ret, (hipStream_t)stream));
 }
 
+B747_API int32_t b747_ppo_gae_population(const float *rew, const float *val, const uint8_t *done,
+                                         const float *last_value, int32_t T, int64_t N, int32_t n_policies,
+                                         int32_t envs_per_policy, const double *hyper_dev, float *adv, float *ret,
+                                         void *stream)
+{
+    const char *const W = "b747_ppo_gae_population";
+    if (int32_t e = check_not_null(W, {{rew, "rew"}, {val, "val"}, {done, "done"}, {last_value, "last_value"},
+                                       {hyper_dev, "hyper_dev"}, {adv, "adv"}, {ret, "ret"}}))
+        return e;
+    if (T < 0) return bad_arg(W, "T < 0");
+    if (N < 0) return bad_arg(W, "N < 0");
+    if (int32_t e = check_pop_groups(W, envs_per_policy, n_policies, "n_policies < 1")) return e;
+    if (N == 0) return 0;
+    // (the upper bound keeps every workgroup's member inside the table)
+    if (N <= (int64_t)(n_policies - 1) * envs_per_policy || N > (int64_t)n_policies * envs_per_policy)
+        return bad_arg(W, "N (outside ((n_policies - 1) * envs_per_policy, n_policies * envs_per_policy])");
+    if (N > (int64_t)kGaeBlock * INT32_MAX) return bad_arg(W, "N (more envs than one grid holds)");
+    if (T == 0) return 0;
+    return launched(W, launch_ppo_gae_population(rew, val, done, last_value, T, N, envs_per_policy, hyper_dev, adv, ret,
+                                                 (hipStream_t)stream));
+}
+
 B747_API int32_t b747_ppo_epoch(float *theta, int32_t obs_dim, const float *obs, const float *act, const float *old_logp,
                                 const float *adv, const float *ret, const int64_t *perm, int64_t n_rows,
                                 int64_t batch_size, double clip_range, double ent_coef, double vf_coef, void *workspace,
@@ -526,6 +548,50 @@ B747_API int32_t b747_ppo_epoch_batched(float *theta, int32_t n_policies, int64_
     return launched(W, launch_ppo_epoch_batched({theta, m, v, t}, n_policies, policy_stride, obs_dim, d, perm, n_rows,
                                                 batch_size, {clip_range, ent_coef, vf_coef}, workspace, workspace_bytes,
                                                 {max_grad_norm, beta1, beta2, eps}, lr_dev, stats, (hipStream_t)stream));
+}
+
+B747_API int32_t b747_ppo_epoch_population_hyper(float *theta, int32_t n_policies, int64_t policy_stride,
+                                                 int32_t obs_dim, const float *obs, const float *act,
+                                                 const float *old_logp, const float *adv, const float *ret,
+                                                 const int64_t *perm, int64_t n_rows, int64_t batch_size,
+                                                 const double *hyper, void *workspace, float *grad, float *m, float *v,
+                                                 int64_t *t, double beta1, double beta2, double eps, float *stats,
+                                                 void *stream)
+{
+    const char *const W = "b747_ppo_epoch_population_hyper";
+    const UpdData d{obs, act, old_logp, adv, ret};
+    if (int32_t e = check_upd_policy(W, theta, obs_dim)) return e;
+    if (int32_t e = check_upd_members(W, n_policies, policy_stride, obs_dim)) return e;
+    if (int32_t e = check_upd_rows(W, d, perm, true, n_rows, batch_size, workspace)) return e;
+    if (int32_t e = check_not_null(W, {{grad, "grad"}, {m, "m"}, {v, "v"}, {t, "t"}})) return e;
+    if (!hyper) return bad_arg(W, "hyper is NULL (a host table, one row of B747_PPO_HYPER_COLS doubles per member)");
+    if (!stats) return bad_arg(W, "stats is NULL");
+    return launched(W, launch_ppo_epoch_population_hyper({theta, m, v, t}, n_policies, policy_stride, obs_dim, d, perm,
+                                                         n_rows, batch_size, hyper, workspace, grad,
+                                                         {0.0, beta1, beta2, eps}, stats, (hipStream_t)stream));
+}
+
+B747_API int32_t b747_ppo_epoch_batched_hyper(float *theta, int32_t n_policies, int64_t policy_stride, int32_t obs_dim,
+                                              const float *obs, const float *act, const float *old_logp,
+                                              const float *adv, const float *ret, const int64_t *perm, int64_t n_rows,
+                                              int64_t batch_size, const double *hyper_dev, void *workspace,
+                                              int64_t workspace_bytes, float *m, float *v, int64_t *t, double beta1,
+                                              double beta2, double eps, float *stats, void *stream)
+{
+    const char *const W = "b747_ppo_epoch_batched_hyper";
+    const UpdData d{obs, act, old_logp, adv, ret};
+    if (int32_t e = check_upd_policy(W, theta, obs_dim)) return e;
+    if (int32_t e = check_upd_members(W, n_policies, policy_stride, obs_dim)) return e;
+    if (int32_t e = check_upd_rows(W, d, perm, true, n_rows, batch_size, workspace)) return e;
+    if (workspace_bytes < upd_pop_ws_bytes(obs_dim, batch_size))
+        return bad_arg(W, "workspace_bytes (below one member's b747_ppo_epoch_batched_workspace(obs_dim, batch_size))");
+    if (int32_t e = check_not_null(W, {{m, "m"}, {v, "v"}, {t, "t"}})) return e;
+    if (!hyper_dev)
+        return bad_arg(W, "hyper_dev is NULL (a device table, one row of B747_PPO_HYPER_COLS doubles per member)");
+    if (!stats) return bad_arg(W, "stats is NULL");
+    return launched(W, launch_ppo_epoch_batched_hyper({theta, m, v, t}, n_policies, policy_stride, obs_dim, d, perm,
+                                                      n_rows, batch_size, hyper_dev, workspace, workspace_bytes,
+                                                      {0.0, beta1, beta2, eps}, stats, (hipStream_t)stream));
 }
 
 B747_API int32_t b747_consts_default(b747_consts *c)

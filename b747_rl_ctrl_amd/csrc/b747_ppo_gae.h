@@ -21,5 +21,13 @@ __attribute__((visibility("hidden"))) hipError_t launch_ppo_gae(const float *rew
                                                                 const float *last_value, int32_t T, int64_t N,
                                                                 double gamma, double gae_lambda, float *adv, float *ret,
                                                                 hipStream_t s);
+// b747_ppo_gae_population's launch: env i takes gamma and gae_lambda from row i / envs_per_policy of the device table
+// hyper_dev (include/b747.h B747_PPO_HYPER_*).  Validated by the caller as above, and envs_per_policy a positive
+// multiple of 64 with N at most n_policies envs_per_policy (no row past the table is read).
+__attribute__((visibility("hidden"))) hipError_t launch_ppo_gae_population(const float *rew, const float *val,
+                                                                           const uint8_t *done, const float *last_value,
+                                                                           int32_t T, int64_t N, int32_t envs_per_policy,
+                                                                           const double *hyper_dev, float *adv,
+                                                                           float *ret, hipStream_t s);
 
 }  // namespace b747

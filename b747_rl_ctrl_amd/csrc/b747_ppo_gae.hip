@@ -9,6 +9,7 @@
 // with g = (float)gamma and gl = (float)(gamma gae_lambda), the double product rounded once.  The multiply by nt
 // stays a multiply (torch's operation sequence, non-finite values included) and nothing contracts into an FMA (the
 // build's -ffp-contract=off, repeated below): the results are torch's bit for bit (tests/test_gpu_ppo_gae.py).
+#include "../../include/b747.h"   // the hyper-parameter table's layout (B747_PPO_HYPER_*)
 #include "b747_ppo_gae.h"
 
 #pragma clang fp contract(off)
@@ -72,23 +73,25 @@ __global__ __launch_bounds__(kGaeBlock) void k_ppo_gae(const float *__restrict__
                                                        float g, float gl, float *__restrict__ adv,
                                                        float *__restrict__ ret)
 {
-    const int64_t i = (int64_t)blockIdx.x * kGaeBlock + threadIdx.x;
-    const bool live = i < N;
-    const int64_t col = live ? i : N - 1;
-    float nv = last_value[col], a = 0.0f;
-    int32_t t = T - 1;
-    GaeRows<U> cur, nxt;
-    gae_load<U>(cur, rew, val, done, t, N, col);
-#pragma unroll 1
-    for (;;) {
-        const int32_t tn = t - U;
-        if (tn >= 0) gae_load<U>(nxt, rew, val, done, tn, N, col);
-        if (t >= U - 1) gae_steps<U, false>(cur, t, N, col, live, g, gl, nv, a, adv, ret);
-        else gae_steps<U, true>(cur, t, N, col, live, g, gl, nv, a, adv, ret);
-        if (tn < 0) break;
-        cur = nxt;
-        t = tn;
-    }
+#include "b747_ppo_gae_body.h"
+}
+
+// k_ppo_gae<U> for a population (b747_ppo_gae_population): env i belongs to member i / envs_per_policy
+// and takes g and gl from that member's row of the hyper-parameter table.  envs_per_policy is a multiple of kGaeBlock
+// (groups = envs_per_policy / kGaeBlock workgroups per member), so the member is uniform over the workgroup and its two
+// doubles are loaded once, here; the product is fp64, rounded once -- launch_ppo_gae's rounding on the host.  A lane
+// past N copies env N - 1: the same wave, so the same member.
+template <int U>
+__global__ __launch_bounds__(kGaeBlock) void k_pop_gae(const float *__restrict__ rew, const float *__restrict__ val,
+                                                       const uint8_t *__restrict__ done,
+                                                       const float *__restrict__ last_value, int32_t T, int64_t N,
+                                                       uint32_t groups, const double *__restrict__ hyper,
+                                                       float *__restrict__ adv, float *__restrict__ ret)
+{
+    const double *row = hyper + (int64_t)(blockIdx.x / groups) * B747_PPO_HYPER_COLS;
+    const double gamma = row[B747_PPO_HYPER_GAMMA], gae_lambda = row[B747_PPO_HYPER_GAE_LAMBDA];
+    const float g = (float)gamma, gl = (float)(gamma * gae_lambda);
+#include "b747_ppo_gae_body.h"
 }
 
 hipError_t launch_ppo_gae(const float *rew, const float *val, const uint8_t *done, const float *last_value, int32_t T,
@@ -97,6 +100,19 @@ hipError_t launch_ppo_gae(const float *rew, const float *val, const uint8_t *don
     const int64_t blocks = (N + kGaeBlock - 1) / kGaeBlock;
     hipLaunchKernelGGL(k_ppo_gae<kGaeUnroll>, dim3((unsigned)blocks), dim3(kGaeBlock), 0, s, rew, val, done, last_value,
                        T, N, (float)gamma, (float)(gamma * gae_lambda), adv, ret);
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_gae_population(const float *rew, const float *val, const uint8_t *done, const float *last_value,
+                                     int32_t T, int64_t N, int32_t envs_per_policy, const double *hyper_dev, float *adv,
+                                     float *ret, hipStream_t s)
+{
+    // a workgroup must lie inside one member (envs_per_policy is a multiple of 64): a build with another block size
+    // (-DB747_GAE_BLOCK, an experiment's) has no population kernel, and says so
+    if (kGaeBlock != 64) return hipErrorInvalidDeviceFunction;
+    const int64_t blocks = (N + kGaeBlock - 1) / kGaeBlock;
+    hipLaunchKernelGGL(k_pop_gae<kGaeUnroll>, dim3((unsigned)blocks), dim3(kGaeBlock), 0, s, rew, val, done, last_value,
+                       T, N, (uint32_t)(envs_per_policy / kGaeBlock), hyper_dev, adv, ret);
     return hipGetLastError();
 }
 

@@ -145,6 +145,19 @@ B747_HIDDEN hipError_t launch_ppo_epoch_batched(const UpdState &st, int n_polici
                                                 int64_t batch_size, const UpdLoss &loss, void *workspace,
                                                 int64_t workspace_bytes, const UpdAdam &adam, const double *lr,
                                                 float *stats, hipStream_t s);
+// The two above with member p's clip_range, ent_coef, vf_coef, max_grad_norm and lr from row p of a hyper-parameter
+// table ([n_policies][B747_PPO_HYPER_COLS] doubles, include/b747.h) in place of loss, adam's
+// max_grad_norm and lr.  launch_ppo_epoch_population_hyper: a HOST table, each member's scalars to launch_ppo_epoch's
+// loop.  launch_ppo_epoch_batched_hyper: a DEVICE table, read by the k_hyp_* kernels by blockIdx.y.
+B747_HIDDEN hipError_t launch_ppo_epoch_population_hyper(const UpdState &st, int n_policies, int64_t policy_stride,
+                                                         int od, const UpdData &d, const int64_t *perm, int64_t n_rows,
+                                                         int64_t batch_size, const double *hyper, void *workspace,
+                                                         float *grad, const UpdAdam &adam, float *stats, hipStream_t s);
+B747_HIDDEN hipError_t launch_ppo_epoch_batched_hyper(const UpdState &st, int n_policies, int64_t policy_stride, int od,
+                                                      const UpdData &d, const int64_t *perm, int64_t n_rows,
+                                                      int64_t batch_size, const double *hyper_dev, void *workspace,
+                                                      int64_t workspace_bytes, const UpdAdam &adam, float *stats,
+                                                      hipStream_t s);
 #undef B747_HIDDEN
 
 #ifndef B747_PPO_UPDATE_NO_KERNELS
@@ -547,6 +560,54 @@ __global__ __launch_bounds__(kUpdAdamBlock) void k_pop_adam(float *__restrict__ 
 {
     constexpr bool POP = true;
     const double lr = lr_dev[blockIdx.y];
+#include "b747_ppo_adam_body.h"
+}
+
+// ---- the member-batched kernels with per-member hyper-parameters (b747_ppo_epoch_batched_hyper).
+// As k_pop_adam does for lr: member p = blockIdx.y loads its values from row p of the device table (hyper_dev is
+// member 0's row; B747_PPO_HYPER_* name the columns) into locals named as the body expects, then runs the unchanged
+// text with POP.  The loads are workgroup-uniform: scalar loads, SGPRs.  k_pop_adv_stats reads no hyper-parameter.
+
+// k_pop_grad<OD> with the member's clip and vf_coef from the table
+template <int OD>
+__global__ __launch_bounds__(256) void k_hyp_grad(const float *__restrict__ theta, const float *__restrict__ obs,
+                                                  const float *__restrict__ act, const float *__restrict__ old_logp,
+                                                  const float *__restrict__ adv, const float *__restrict__ ret,
+                                                  const int64_t *__restrict__ idx, int64_t batch,
+                                                  const double *__restrict__ hyper_dev,
+                                                  const double *__restrict__ adv_part, float *__restrict__ gpart,
+                                                  double *__restrict__ spart, UpdPopArgs pa)
+{
+    constexpr bool POP = true;
+    const double *hyp = hyper_dev + (int64_t)blockIdx.y * B747_PPO_HYPER_COLS;
+    const double clip = hyp[B747_PPO_HYPER_CLIP_RANGE], vf_coef = hyp[B747_PPO_HYPER_VF_COEF];
+#include "b747_ppo_grad_body.h"
+}
+
+// k_pop_reduce with the member's ent_coef and vf_coef from the table, rounded to float here (the launcher's rounding
+// of k_pop_reduce's arguments)
+__global__ __launch_bounds__(256) void k_hyp_reduce(const float *__restrict__ gpart, const double *__restrict__ spart,
+                                                    int n_wg, int n_params, int ba_at, int bv_at, int log_std_at,
+                                                    const float *__restrict__ theta, int64_t batch,
+                                                    const double *__restrict__ hyper_dev, float *__restrict__ grad,
+                                                    float *__restrict__ stats, UpdPopArgs pa)
+{
+    constexpr bool POP = true;
+    const double *hyp = hyper_dev + (int64_t)blockIdx.y * B747_PPO_HYPER_COLS;
+    const float ent_coef = (float)hyp[B747_PPO_HYPER_ENT_COEF], vf_coef = (float)hyp[B747_PPO_HYPER_VF_COEF];
+#include "b747_ppo_reduce_body.h"
+}
+
+// k_pop_adam with the member's max_norm and lr from the table
+__global__ __launch_bounds__(kUpdAdamBlock) void k_hyp_adam(float *__restrict__ theta, float *__restrict__ m,
+                                                            float *__restrict__ v, int64_t *__restrict__ t,
+                                                            const float *__restrict__ grad, int64_t n, double grad_scale,
+                                                            const double *__restrict__ hyper_dev, double beta1,
+                                                            double beta2, double eps, UpdPopArgs pa)
+{
+    constexpr bool POP = true;
+    const double *hyp = hyper_dev + (int64_t)blockIdx.y * B747_PPO_HYPER_COLS;
+    const double max_norm = hyp[B747_PPO_HYPER_MAX_GRAD_NORM], lr = hyp[B747_PPO_HYPER_LR];
 #include "b747_ppo_adam_body.h"
 }
 

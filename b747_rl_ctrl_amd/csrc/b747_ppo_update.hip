@@ -103,6 +103,52 @@ hipError_t epoch_batched_od(const UpdState &st, int n_policies, int64_t policy_s
     return hipSuccess;
 }
 
+// b747_ppo_epoch_batched_hyper's loops: epoch_batched_od's chunks, grids and launch order with the k_hyp_* kernels,
+// which read their member's hyper-parameters from the device table.  The table pointer passed is the row of the
+// chunk's first member (as lr + c0 above); the kernels add blockIdx.y rows.
+template <int OD>
+hipError_t epoch_batched_hyper_od(const UpdState &st, int n_policies, int64_t policy_stride, const UpdData &d,
+                                  const int64_t *perm, int64_t n_rows, int64_t batch_size, const double *hyper_dev,
+                                  void *workspace, int64_t workspace_bytes, const UpdAdam &adam, float *stats,
+                                  hipStream_t s)
+{
+    constexpr PolicyLayout L = PolicyLayout::of(OD);
+    constexpr int P = L.total;
+    const hipError_t attr = grad_lds_limit<OD>(&k_hyp_grad<OD>);
+    if (attr != hipSuccess) return attr;
+    const int64_t per = upd_pop_ws_bytes(OD, batch_size), n_mb = (n_rows + batch_size - 1) / batch_size;
+    int64_t chunk = workspace_bytes / per;
+    if (chunk > n_policies) chunk = n_policies;
+    if (chunk > kUpdPopMaxMembers) chunk = kUpdPopMaxMembers;
+    const UpdPopArgs pa{policy_stride, P, n_rows, per, n_mb * kUpdStats};
+    char *ws = static_cast<char *>(workspace);
+    double *adv_part = reinterpret_cast<double *>(ws + upd_ws_adv());
+    double *spart = reinterpret_cast<double *>(ws + upd_ws_sums());
+    float *gpart = reinterpret_cast<float *>(ws + upd_pop_ws_grad(batch_size));
+    float *grad = reinterpret_cast<float *>(ws + upd_pop_ws_out(OD, batch_size));
+    for (int64_t c0 = 0; c0 < n_policies; c0 += chunk) {
+        const unsigned members = (unsigned)(n_policies - c0 < chunk ? n_policies - c0 : chunk);
+        float *th = st.theta + c0 * policy_stride, *row = stats + c0 * n_mb * kUpdStats;
+        const int64_t *pm = perm + c0 * n_rows;
+        const double *hyp = hyper_dev + c0 * B747_PPO_HYPER_COLS;
+        for (int64_t at = 0; at < n_rows; at += batch_size, row += kUpdStats) {
+            const int64_t batch = n_rows - at < batch_size ? n_rows - at : batch_size;
+            const int n_wg = upd_n_wg(batch);
+            hipLaunchKernelGGL(k_pop_adv_stats, dim3(kUpdAdvBlocks, members), dim3(256), 0, s, d.adv, pm + at, batch,
+                               adv_part, pa);
+            hipLaunchKernelGGL(k_hyp_grad<OD>, dim3(n_wg, members), dim3(256), UpdLds<OD>::bytes, s, th, d.obs, d.act,
+                               d.old_logp, d.adv, d.ret, pm + at, batch, hyp, adv_part, gpart, spart, pa);
+            hipLaunchKernelGGL(k_hyp_reduce, dim3((P + 1 + 255) / 256, members), dim3(256), 0, s, gpart, spart, n_wg, P,
+                               L.ba, L.bv, L.log_std, th, batch, hyp, grad, row, pa);
+            hipLaunchKernelGGL(k_hyp_adam, dim3(1, members), dim3(kUpdAdamBlock), 0, s, th, st.m + c0 * P, st.v + c0 * P,
+                               st.t + c0, grad, (int64_t)P, 1.0, hyp, adam.beta1, adam.beta2, adam.eps, pa);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
 }  // namespace
 
 hipError_t launch_ppo_grad(const float *theta, int od, const UpdData &d, const int64_t *idx, int64_t batch,
@@ -158,6 +204,39 @@ hipError_t launch_ppo_epoch_batched(const UpdState &st, int n_policies, int64_t 
     return with_obs_dim(od, hipErrorInvalidValue, [&](auto OD) {
         return epoch_batched_od<OD()>(st, n_policies, policy_stride, d, perm, n_rows, batch_size, loss, workspace,
                                       workspace_bytes, adam, lr, stats, s);
+    });
+}
+
+// (adam.max_grad_norm is not read by the two below: the table's column takes its place)
+hipError_t launch_ppo_epoch_population_hyper(const UpdState &st, int n_policies, int64_t policy_stride, int od,
+                                             const UpdData &d, const int64_t *perm, int64_t n_rows, int64_t batch_size,
+                                             const double *hyper, void *workspace, float *grad, const UpdAdam &adam,
+                                             float *stats, hipStream_t s)
+{
+    return with_obs_dim(od, hipErrorInvalidValue, [&](auto OD) {
+        constexpr int64_t P = PolicyLayout::of(OD()).total;
+        const int64_t n_mb = (n_rows + batch_size - 1) / batch_size;
+        for (int64_t p = 0; p < n_policies; ++p) {
+            const double *h = hyper + p * B747_PPO_HYPER_COLS;
+            const UpdState member{st.theta + p * policy_stride, st.m + p * P, st.v + p * P, st.t + p};
+            const UpdLoss loss{h[B747_PPO_HYPER_CLIP_RANGE], h[B747_PPO_HYPER_ENT_COEF], h[B747_PPO_HYPER_VF_COEF]};
+            const UpdAdam mine{h[B747_PPO_HYPER_MAX_GRAD_NORM], adam.beta1, adam.beta2, adam.eps};
+            const hipError_t e = epoch_od<OD()>(member, d, perm + p * n_rows, n_rows, batch_size, loss, workspace, grad,
+                                                mine, h[B747_PPO_HYPER_LR], stats + p * n_mb * kUpdStats, s);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    });
+}
+
+hipError_t launch_ppo_epoch_batched_hyper(const UpdState &st, int n_policies, int64_t policy_stride, int od,
+                                          const UpdData &d, const int64_t *perm, int64_t n_rows, int64_t batch_size,
+                                          const double *hyper_dev, void *workspace, int64_t workspace_bytes,
+                                          const UpdAdam &adam, float *stats, hipStream_t s)
+{
+    return with_obs_dim(od, hipErrorInvalidValue, [&](auto OD) {
+        return epoch_batched_hyper_od<OD()>(st, n_policies, policy_stride, d, perm, n_rows, batch_size, hyper_dev,
+                                            workspace, workspace_bytes, adam, stats, s);
     });
 }
 

@@ -192,6 +192,62 @@ class PPOConfig:
     batch_size: int = 65536
 
 
+# The per-member hyper-parameter table of a population (include/b747.h B747_PPO_HYPER_*): [P, 8] float64,
+# one 64-byte row per member, column 7 reserved (0).  The keys are PPOConfig's names.
+HYPER_COLS = 8
+HYPER_COLUMN = {"learning_rate": 0, "clip_range": 1, "ent_coef": 2, "vf_coef": 3, "max_grad_norm": 4, "gamma": 5,
+                "gae_lambda": 6}
+
+
+def _check_hyper_value(key: str, x, where: str) -> float:
+    """x as a float if it is a value `key` may take: finite; gamma and gae_lambda in [0, 1]; clip_range, learning_rate
+    and max_grad_norm above 0; ent_coef and vf_coef not negative"""
+    x = float(x)
+    if not math.isfinite(x):
+        raise ValueError(f"{where}: {key} = {x} is not finite")
+    if key in ("gamma", "gae_lambda"):
+        if not 0.0 <= x <= 1.0:
+            raise ValueError(f"{where}: {key} = {x} is outside [0, 1]")
+    elif key in ("clip_range", "learning_rate", "max_grad_norm"):
+        if not x > 0.0:
+            raise ValueError(f"{where}: {key} = {x} is not above 0")
+    elif x < 0.0:
+        raise ValueError(f"{where}: {key} = {x} is negative")
+    return x
+
+
+def hyper_table(cfg: PPOConfig, n_members: int, hyper=None, learning_rates=None) -> torch.Tensor:
+    """The [n_members, 8] float64 CPU table of per-member hyper-parameters (columns HYPER_COLUMN, the last one 0).
+    hyper: None or one dict per member with keys among learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm,
+    gamma and gae_lambda; a key a member does not name comes from cfg -- the learning rate from learning_rates[p] where
+    that list is given (then no dict may name learning_rate: one source per value).  ValueError for an unknown key, a
+    list of the wrong length or a value outside its range (_check_hyper_value).  n_steps, batch_size, n_epochs and the
+    network are not keys: they change shapes, and stay the population's."""
+    P = int(n_members)
+    if P < 1:
+        raise ValueError(f"hyper_table: {P} members")
+    rows = [{}] * P if hyper is None else list(hyper)
+    if len(rows) != P or (learning_rates is not None and len(learning_rates) != P):
+        raise ValueError("hyper_table: hyper and learning_rates take one entry per member")
+    table = torch.zeros(P, HYPER_COLS, dtype=torch.float64)
+    for p, row in enumerate(rows):
+        unknown = sorted(set(row) - set(HYPER_COLUMN))
+        if unknown:
+            raise ValueError(f"hyper_table: member {p}: unknown key(s) {unknown}; a member's own values are "
+                             f"{sorted(HYPER_COLUMN)} (n_steps, batch_size, n_epochs and the network are shared)")
+        if learning_rates is not None and "learning_rate" in row:
+            raise ValueError(f"hyper_table: member {p} names learning_rate although learning_rates is given")
+        for key, col in HYPER_COLUMN.items():
+            if key in row:
+                x = row[key]
+            elif key == "learning_rate" and learning_rates is not None:
+                x = learning_rates[p]
+            else:
+                x = getattr(cfg, key)
+            table[p, col] = _check_hyper_value(key, x, f"hyper_table: member {p}")
+    return table
+
+
 class PPO:
     """Device-resident PPO on a BatchControllerEnv (action space [-1, 1] with norm_act)."""
 
@@ -594,7 +650,7 @@ class PopulationPPO:
     built after torch.manual_seed(seeds[p]): what PPO(seed=seeds[p]) builds), its own reward constants
     (rew_configs[p], a reward_config dict as BatchControllerEnv.set_rew_config takes; None = the env's) and its own
     learning rate; gamma, gae_lambda, the clip range, the epochs and the batch size (rows of ONE member per minibatch) are
-    cfg's, shared.  This is the shape of the reference's ControllerAgent.optimize() (neural/agent.py:89-136): trials
+    cfg's, shared (the first three and the loss coefficients per member with `hyper`, below).  This is the shape of the reference's ControllerAgent.optimize() (neural/agent.py:89-136): trials
     that differ in reward_config and hyper-parameters, ranked by ControlTestCallback.mean_quality -- step_tests()
     here.  The update is PPO(fused_update=True, epoch_call=True)'s, per member, from one C call per epoch
     (b747_ppo_epoch_population): the same kernels, the same bits as P separate learners
@@ -604,7 +660,17 @@ class PopulationPPO:
 
     batched_update=True (opt-in) makes the epoch call b747_ppo_epoch_batched: four launches per minibatch
     for all members (the member on blockIdx.y of member-batched update kernels) in place of four per member -- the same
-    bits (tests/test_gpu_ppo_population_batched_train.py), a workspace slice per member instead of one shared."""
+    bits (tests/test_gpu_ppo_population_batched_train.py), a workspace slice per member instead of one shared.
+
+    hyper (a list of one dict per member, as hyper_table takes) gives every member its own gamma,
+    gae_lambda, clip_range, ent_coef, vf_coef, max_grad_norm and learning_rate -- the reference's PPO trial space
+    (neural/setups.py, trial_hyperparams).  The values live in a [P, 8] float64 table, `hyper` on the CPU and
+    `hyper_dev` on the env's device: compute_gae then is one b747_ppo_gae_population launch and the epoch call
+    b747_ppo_epoch_population_hyper (b747_ppo_epoch_batched_hyper with batched_update) -- per member the bits of a
+    separate learner with those values (tests/test_gpu_ppo_population_hyper_train.py).  set_hyper changes a member's
+    values between iterations and copy_member copies one member onto another (the exploit step of a population-based
+    schedule), neither rebuilding a buffer.  n_steps, batch_size, n_epochs and the network stay shared: they change
+    shapes, not values.  With hyper=None nothing changes: the calls and the bits are those described above."""
 
     # The batched update's workspace holds one slice per member (b747_ppo_epoch_batched_workspace: ~9 MB at the full
     # 256-workgroup grid, ~80 kB at batch 256) so that all members run in one launch; past this many bytes the call
@@ -614,7 +680,7 @@ class PopulationPPO:
 
     def __init__(self, env: BatchControllerEnv, n_members: int, envs_per_member: int = 64,
                  cfg: Optional[PPOConfig] = None, seeds=None, rew_configs=None, learning_rates=None, seed: int = 0,
-                 batched_update: bool = False):
+                 batched_update: bool = False, hyper=None):
         from . import _lib
         from .evaluate import pack_policies
         self._lib, self._L = _lib, _lib.lib()
@@ -628,6 +694,10 @@ class PopulationPPO:
         lrs = [self.cfg.learning_rate] * P if learning_rates is None else [float(x) for x in learning_rates]
         if len(self.seeds) != P or len(lrs) != P or (rew_configs is not None and len(rew_configs) != P):
             raise ValueError("PopulationPPO: seeds, rew_configs and learning_rates take one entry per member")
+        # (hyper: the table holds every member's values; built first, so that a refused value raises before any launch)
+        self.hyper = None if hyper is None else hyper_table(self.cfg, P, hyper, learning_rates)
+        if self.hyper is not None:
+            lrs = self.hyper[:, HYPER_COLUMN["learning_rate"]].tolist()
         self.learning_rates = lrs
         self._lr = (ctypes.c_double * P)(*lrs)            # b747_ppo_epoch_population reads them on the host
         nets = []
@@ -656,6 +726,7 @@ class PopulationPPO:
             self.lr_dev = torch.tensor(lrs, dtype=torch.float64, device=dev)      # b747_ppo_epoch_batched reads them there
             self.upd_ws_batched = torch.empty(max(1, min(P, self.BATCHED_WORKSPACE_CAP // per)) * per, dtype=torch.uint8,
                                               device=dev)
+        self.hyper_dev = None if self.hyper is None else self.hyper.to(dev)   # the kernels read it there, when they run
         (self.obs_buf, self.act_buf, self.logp_buf, self.val_buf, self.rew_buf, self.done_buf, self.adv_buf,
          self.ret_buf) = _rollout_buffers(T, n, od, dev)
         self.last_val = z(n)
@@ -682,8 +753,15 @@ class PopulationPPO:
     @torch.no_grad()
     def compute_gae(self, T: Optional[int] = None):
         """PPO.compute_gae for every member: one b747_ppo_gae launch over all N envs, bootstrapped with the rollout
-        kernel's last_val"""
+        kernel's last_val (with hyper: one b747_ppo_gae_population launch, each member's gamma and gae_lambda from its
+        row of hyper_dev)"""
         T, c, p = T or self.cfg.n_steps, self.cfg, _p
+        if self.hyper is not None:
+            self._lib.check(self._L.b747_ppo_gae_population(
+                p(self.rew_buf), p(self.val_buf), p(self.done_buf), p(self.last_val), T, self.env.n, self.n_members,
+                self.envs_per_member, p(self.hyper_dev), p(self.adv_buf), p(self.ret_buf),
+                torch.cuda.current_stream().cuda_stream), "b747_ppo_gae_population")
+            return
         self._lib.check(self._L.b747_ppo_gae(
             p(self.rew_buf), p(self.val_buf), p(self.done_buf), p(self.last_val), T, self.env.n, c.gamma, c.gae_lambda,
             p(self.adv_buf), p(self.ret_buf), torch.cuda.current_stream().cuda_stream), "b747_ppo_gae")
@@ -700,8 +778,8 @@ class PopulationPPO:
     def train(self, T: Optional[int] = None,
               minibatch_order: Optional[Callable[[int, int, int, int], torch.Tensor]] = None):
         """PPO.train(fused_update, epoch_call) for every member: per epoch one sample order per member and ONE
-        b747_ppo_epoch_population call (b747_ppo_epoch_batched with batched_update); afterwards one
-        b747_policy_pack_batch.
+        b747_ppo_epoch_population call (b747_ppo_epoch_batched with batched_update; their _hyper forms with hyper, which
+        take the members' values from the table); afterwards one b747_policy_pack_batch.
         minibatch_order(epoch, T, envs_per_member, p) -> [T * envs_per_member] indices into MEMBER p's own time-major
         rows (t * envs_per_member + j: what PPO.train's hook gives a learner that has the member's envs to itself);
         default torch.randperm.  Returns PPO.train's names as [P] tensors (float64; explained_variance and std
@@ -721,6 +799,19 @@ class PopulationPPO:
                                      for m in range(P)])
             assert tuple(local.shape) == (P, n_rows), "minibatch_order must give every row of the member once"
             perm = torch.gather(rows_of, 1, local).contiguous()       # member rows -> rows t * N + i of the buffers
+            if self.hyper is not None:
+                head = (p(self.flat), P, self.stride, self.env.obs_dim, p(self.obs_buf), p(self.act_buf),
+                        p(self.logp_buf), p(self.adv_buf), p(self.ret_buf), p(perm), n_rows, c.batch_size)
+                tail = (p(self.upd_m), p(self.upd_v), p(self.upd_t), 0.9, 0.999, 1e-5, p(stats[epoch]),
+                        torch.cuda.current_stream().cuda_stream)
+                if self.batched_update:
+                    self._lib.check(self._L.b747_ppo_epoch_batched_hyper(
+                        *head, p(self.hyper_dev), p(self.upd_ws_batched), self.upd_ws_batched.numel(), *tail),
+                        "b747_ppo_epoch_batched_hyper")
+                else:       # (the host table: this call reads it before it returns)
+                    self._lib.check(self._L.b747_ppo_epoch_population_hyper(
+                        *head, p(self.hyper), p(self.upd_ws), p(self.upd_grad), *tail), "b747_ppo_epoch_population_hyper")
+                continue
             if self.batched_update:
                 self._lib.check(self._L.b747_ppo_epoch_batched(
                     p(self.flat), P, self.stride, self.env.obs_dim, p(self.obs_buf), p(self.act_buf), p(self.logp_buf),
@@ -760,6 +851,47 @@ class PopulationPPO:
             st["mean_reward"] = self.rew_buf[:T].reshape(T, P, epp).mean(dim=(0, 2))
             hist.append(st)
         return hist
+
+    def _need_hyper(self, what: str, *members):
+        if self.hyper is None:
+            raise ValueError(f"PopulationPPO.{what}: the population was built with hyper=None (its hyper-parameters are "
+                             f"cfg's, kernel arguments shared by the members)")
+        for m in members:
+            if not 0 <= int(m) < self.n_members:
+                raise ValueError(f"PopulationPPO.{what}: member {m} of {self.n_members}")
+
+    def set_hyper(self, p: int, **kw):
+        """Change hyper-parameters of member p (keys as hyper_table's, validated the same way): the CPU row, then one
+        stream-ordered copy of that row into hyper_dev -- the launches that follow on the stream read the new values.
+        No buffer is rebuilt, and a captured graph of the population's calls stays valid (the kernels read the table
+        when they run)."""
+        self._need_hyper("set_hyper", p)
+        unknown = sorted(set(kw) - set(HYPER_COLUMN))
+        if unknown:
+            raise ValueError(f"PopulationPPO.set_hyper: unknown key(s) {unknown}; a member's own values are "
+                             f"{sorted(HYPER_COLUMN)}")
+        new = {k: _check_hyper_value(k, x, f"PopulationPPO.set_hyper: member {p}") for k, x in kw.items()}
+        for k, x in new.items():            # (nothing is written before every value has passed)
+            self.hyper[p, HYPER_COLUMN[k]] = x
+        self.learning_rates[p] = float(self.hyper[p, HYPER_COLUMN["learning_rate"]])
+        self._lr[p] = self.learning_rates[p]
+        self.hyper_dev[p].copy_(self.hyper[p], non_blocking=True)
+
+    def copy_member(self, src: int, dst: int, hyper: bool = True):
+        """Member src's parameters (the whole stride of flat: the packed sections travel with them), Adam moments and
+        step count onto member dst, and with `hyper` its table row too: device copies on the current stream, no
+        synchronisation -- the exploit step of a population-based schedule, and what optimize()'s "keep the best"
+        needs.  The members' envs, reward constants and rollout rows stay their own."""
+        self._need_hyper("copy_member", src, dst)
+        if int(src) == int(dst):
+            return
+        for x in (self.flat, self.upd_m, self.upd_v, self.upd_t):
+            x[dst].copy_(x[src])
+        if hyper:
+            self.hyper[dst] = self.hyper[src]
+            self.learning_rates[dst] = self.learning_rates[src]
+            self._lr[dst] = self._lr[src]
+            self.hyper_dev[dst].copy_(self.hyper_dev[src])
 
     def member(self, p: int) -> ActorCritic:
         """A copy of member p's policy as an ActorCritic on the env's device"""

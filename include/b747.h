@@ -39,7 +39,8 @@ extern "C" {
                                 * 12: + b747_ppo_update_workspace, b747_ppo_grad, b747_ppo_adam; 13: + b747_ppo_gae,
                                 * b747_ppo_epoch, b747_get_specialization; 14: + b747_ppo_rollout_lanes; 15: + b747_eval_population,
                                 * b747_policy_pack_batch.  b747_ppo_rollout_population, b747_ppo_epoch_population,
-                                * b747_ppo_epoch_batched_workspace and b747_ppo_epoch_batched
+                                * b747_ppo_epoch_batched_workspace and b747_ppo_epoch_batched, then
+                                * b747_ppo_gae_population, b747_ppo_epoch_population_hyper and b747_ppo_epoch_batched_hyper
                                 * came later as purely additive entry points under 15 (no struct, argument or
                                 * behaviour of an existing one changed): a library built before them still reports
                                 * 15, and a binding catches it by the missing entry point (_lib.bind) */
@@ -522,6 +523,52 @@ int32_t b747_ppo_epoch_batched(float *theta /* [n_policies][policy_stride] */, i
                                const double *lr_dev /* device, [n_policies] */, double beta1, double beta2, double eps,
                                float *stats /* [n_policies][ceil(n_rows / batch_size)][8] */, void *stream);
 
+/* ---- per-member PPO hyper-parameters for a population (additive under ABI 15) ----
+ * A hyper-parameter table is [n_policies][B747_PPO_HYPER_COLS] doubles, one 64-byte row per member, the columns named
+ * below.  Every entry point that takes one takes this layout -- as a HOST table (hyper) or a DEVICE table (hyper_dev),
+ * as its comment says -- and reads only its own columns; the reserved column is written 0 and never read.  What a
+ * member cannot have of its own are the values that change shapes: n_steps, batch_size, the number of epochs and the
+ * network's architecture stay the population's. */
+#define B747_PPO_HYPER_COLS 8
+#define B747_PPO_HYPER_LR 0             /* torch.optim.Adam's lr */
+#define B747_PPO_HYPER_CLIP_RANGE 1
+#define B747_PPO_HYPER_ENT_COEF 2
+#define B747_PPO_HYPER_VF_COEF 3
+#define B747_PPO_HYPER_MAX_GRAD_NORM 4
+#define B747_PPO_HYPER_GAMMA 5
+#define B747_PPO_HYPER_GAE_LAMBDA 6     /* (column 7: reserved) */
+/* b747_ppo_epoch_population with member p's clip_range, ent_coef, vf_coef, max_grad_norm and lr taken from row p of
+ * the HOST table hyper [n_policies][8] in place of the five arguments: the same host loop over the members of
+ * b747_ppo_epoch's launches, each with its member's scalars as kernel arguments -- the bits of n_policies
+ * b747_ppo_epoch calls with those scalars.  The table is read during the call only.  Validation:
+ * b747_ppo_epoch_population's checks, and hyper != NULL (its values are the caller's to check: ppo.hyper_table). */
+int32_t b747_ppo_epoch_population_hyper(float *theta /* [n_policies][policy_stride] */, int32_t n_policies,
+                                        int64_t policy_stride, int32_t obs_dim, const float *obs, const float *act,
+                                        const float *old_logp, const float *adv, const float *ret,
+                                        const int64_t *perm /* [n_policies][n_rows] */, int64_t n_rows,
+                                        int64_t batch_size, const double *hyper /* host, [n_policies][8] */,
+                                        void *workspace, float *grad /* [P], reused */, float *m,
+                                        float *v /* [n_policies][P] */, int64_t *t /* [n_policies] */, double beta1,
+                                        double beta2, double eps,
+                                        float *stats /* [n_policies][ceil(n_rows / batch_size)][8] */, void *stream);
+/* b747_ppo_epoch_batched with the DEVICE table hyper_dev [n_policies][8] in place of clip_range, ent_coef, vf_coef,
+ * max_grad_norm and lr_dev: the same chunks, grids and launch order, with siblings of three of its kernels (k_hyp_grad,
+ * k_hyp_reduce, k_hyp_adam) that load member blockIdx.y's values from its table row -- workgroup-uniform loads -- before
+ * they run the unchanged kernel text; ent_coef and vf_coef are rounded to float in the reduce kernel, as the host does
+ * for b747_ppo_epoch_batched.  theta, m, v, t and stats get the bits of b747_ppo_epoch_population_hyper on the same
+ * table.  The table is read when the kernels run: a row changed on the stream between two calls (or two replays of a
+ * captured call) holds from the next one on.  Its values cannot be checked here.  workspace:
+ * b747_ppo_epoch_batched_workspace's, unchanged.  Validation: b747_ppo_epoch_batched's checks with hyper_dev != NULL for
+ * lr_dev's.  Stream-ordered, graph-capturable, allocates nothing, synchronises nothing, reads nothing back. */
+int32_t b747_ppo_epoch_batched_hyper(float *theta /* [n_policies][policy_stride] */, int32_t n_policies,
+                                     int64_t policy_stride, int32_t obs_dim, const float *obs, const float *act,
+                                     const float *old_logp, const float *adv, const float *ret,
+                                     const int64_t *perm /* [n_policies][n_rows] */, int64_t n_rows, int64_t batch_size,
+                                     const double *hyper_dev /* device, [n_policies][8] */, void *workspace,
+                                     int64_t workspace_bytes, float *m, float *v /* [n_policies][P] */,
+                                     int64_t *t /* [n_policies] */, double beta1, double beta2, double eps,
+                                     float *stats /* [n_policies][ceil(n_rows / batch_size)][8] */, void *stream);
+
 /* ---- generalized advantage estimation in one launch (ABI 13; PPO.compute_gae, SB3 1.4
  * RolloutBuffer.compute_returns_and_advantage) ----
  * rew, val, adv, ret [T][N] float and done [T][N] bytes (0 / 1), time-major (row t * N + i); last_value [N]: the value
@@ -536,6 +583,21 @@ int32_t b747_ppo_epoch_batched(float *theta /* [n_policies][policy_stride] */, i
  * Stream-ordered, graph-capturable, no allocation. */
 int32_t b747_ppo_gae(const float *rew, const float *val, const uint8_t *done, const float *last_value,
                      int32_t T, int64_t N, double gamma, double gae_lambda, float *adv, float *ret, void *stream);
+/* b747_ppo_gae for a population (additive under ABI 15): env i belongs to member i / envs_per_policy and
+ * runs b747_ppo_gae's recurrence with g = (float)gamma and gl = (float)(gamma * gae_lambda) of that member's row of the
+ * DEVICE table hyper_dev [n_policies][B747_PPO_HYPER_COLS] (columns B747_PPO_HYPER_GAMMA and _GAE_LAMBDA; the product
+ * in fp64, rounded once, in the kernel: the host's rounding in b747_ppo_gae) -- the bits of one b747_ppo_gae call per
+ * member on its own columns with its own scalars.  One lane per env, one launch; a workgroup is one wave, so its
+ * member is uniform and the two doubles are loaded once.  The table is read when the kernel runs (see
+ * b747_ppo_epoch_batched_hyper); its values cannot be checked here.  -hipErrorInvalidValue before anything reaches the
+ * device (b747_last_error names the argument) for a NULL pointer, T < 0, N < 0, n_policies < 1, envs_per_policy not a
+ * positive multiple of 64, or -- with N > 0 -- N outside ((n_policies - 1) * envs_per_policy, n_policies *
+ * envs_per_policy] (the last member may be partial); T == 0 or N == 0 returns 0 and launches nothing.  Stream-ordered,
+ * graph-capturable, no allocation. */
+int32_t b747_ppo_gae_population(const float *rew, const float *val, const uint8_t *done, const float *last_value,
+                                int32_t T, int64_t N, int32_t n_policies, int32_t envs_per_policy,
+                                const double *hyper_dev /* device, [n_policies][8] */, float *adv, float *ret,
+                                void *stream);
 
 /* Human-readable text of the last error returned on this thread. */
 const char *b747_last_error(void);
