@@ -110,6 +110,8 @@ SIGNATURES = {
                                         + [_F64, _F64, _F64, _V, _V], _I32),
     "b747_ppo_epoch_batched_hyper": ([_V, _I32, _I64, _I32] + [_V] * 6 + [_I64, _I64, _V, _V, _I64] + [_V] * 3
                                      + [_F64, _F64, _F64, _V, _V], _I32),
+    # (the population's sample orders drawn on the device: perm, n_policies, T, envs_per_policy, N, seed, step_base, epoch)
+    "b747_ppo_sample_orders": ([_V, _I32, _I32, _I32, _I64, _U64, _V, _U32, _V], _I32),
 }
 
 

@@ -29,6 +29,7 @@
 #define B747_PPO_UPDATE_NO_KERNELS   // the update kernels live in b747_ppo_update.hip; this unit calls their launchers
 #include "b747_ppo_update.h"
 #include "b747_ppo_gae.h"
+#include "b747_ppo_order.h"
 
 using namespace b747;
 
@@ -480,6 +481,22 @@ B747_API int32_t b747_ppo_gae_population(const float *rew, const float *val, con
     if (T == 0) return 0;
     return launched(W, launch_ppo_gae_population(rew, val, done, last_value, T, N, envs_per_policy, hyper_dev, adv, ret,
                                                  (hipStream_t)stream));
+}
+
+B747_API int32_t b747_ppo_sample_orders(int64_t *perm, int32_t n_policies, int32_t T, int32_t envs_per_policy, int64_t N,
+                                        uint64_t seed, const uint64_t *step_base, uint32_t epoch, void *stream)
+{
+    const char *const W = "b747_ppo_sample_orders";
+    if (int32_t e = check_not_null(W, {{perm, "perm"}})) return e;
+    if (T < 0) return bad_arg(W, "T < 0");
+    if (int32_t e = check_pop_groups(W, envs_per_policy, n_policies, "n_policies < 1")) return e;
+    if ((int64_t)n_policies * envs_per_policy > N)
+        return bad_arg(W, "N (fewer envs than n_policies * envs_per_policy: a member's rows would lie outside the rollout)");
+    if ((int64_t)T * envs_per_policy > kOrderMaxRows)
+        return bad_arg(W, "T * envs_per_policy > 16384 (one workgroup sorts a member's keys in LDS, 8 bytes each)");
+    if (T == 0) return 0;
+    return launched(W, launch_ppo_sample_orders(perm, n_policies, T, envs_per_policy, N, seed, step_base, epoch,
+                                                (hipStream_t)stream));
 }
 
 B747_API int32_t b747_ppo_epoch(float *theta, int32_t obs_dim, const float *obs, const float *act, const float *old_logp,

@@ -670,7 +670,15 @@ class PopulationPPO:
     separate learner with those values (tests/test_gpu_ppo_population_hyper_train.py).  set_hyper changes a member's
     values between iterations and copy_member copies one member onto another (the exploit step of a population-based
     schedule), neither rebuilding a buffer.  n_steps, batch_size, n_epochs and the network stay shared: they change
-    shapes, not values.  With hyper=None nothing changes: the calls and the bits are those described above."""
+    shapes, not values.  With hyper=None nothing changes: the calls and the bits are those described above.
+
+    sample_order="device" (opt-in) draws every epoch's sample orders for all members with ONE
+    b747_ppo_sample_orders launch into the persistent `perm` buffer, in place of a torch.randperm per member, a stack and
+    a gather on the host: a counter-based stream keyed by (seed, step_base, epoch, member), so the random streams are
+    not the default's ("host": torch's generator, today's calls and bits) and train() takes no minibatch_order hook.  A
+    member's rows are limited to 16,384 (n_steps * envs_per_member; the kernel sorts them in LDS).  With it no host
+    randomness is left in an iteration, and learn(use_graph=True) replays rollout, GAE, the epochs and the repack as one
+    HIP graph per iteration (with batched_update=True, whose calls read every per-member value on the device)."""
 
     # The batched update's workspace holds one slice per member (b747_ppo_epoch_batched_workspace: ~9 MB at the full
     # 256-workgroup grid, ~80 kB at batch 256) so that all members run in one launch; past this many bytes the call
@@ -680,7 +688,7 @@ class PopulationPPO:
 
     def __init__(self, env: BatchControllerEnv, n_members: int, envs_per_member: int = 64,
                  cfg: Optional[PPOConfig] = None, seeds=None, rew_configs=None, learning_rates=None, seed: int = 0,
-                 batched_update: bool = False, hyper=None):
+                 batched_update: bool = False, hyper=None, sample_order: str = "host"):
         from . import _lib
         from .evaluate import pack_policies
         self._lib, self._L = _lib, _lib.lib()
@@ -690,6 +698,17 @@ class PopulationPPO:
         if P < 1 or epp < 64 or epp % 64 != 0 or not ((P - 1) * epp < n <= P * epp):
             raise ValueError(f"PopulationPPO: {P} members of {epp} envs (a positive multiple of 64) do not tile the "
                              f"env's {n} envs (the last member may be partial)")
+        if sample_order not in ("host", "device"):
+            raise ValueError(f"PopulationPPO: sample_order={sample_order!r}: \"host\" or \"device\"")
+        self.sample_order = sample_order
+        self._graph, self._graph_key = None, None
+        if sample_order == "device":
+            # the persistent order buffer, and the first draw into it (epoch 0 at step_base 0; train() draws again): the
+            # entry point refuses a member of more rows than it sorts, or envs that the members do not cover, before
+            # anything reaches the device
+            self.perm = torch.empty(P, self.cfg.n_steps * epp, dtype=torch.int64, device=dev)
+            if self._sample_orders(0, self.cfg.n_steps, None) != 0:
+                raise ValueError(f"PopulationPPO(sample_order=\"device\"): {self._L.b747_last_error().decode()}")
         self.seeds = [self.seed + p for p in range(P)] if seeds is None else [int(s) for s in seeds]
         lrs = [self.cfg.learning_rate] * P if learning_rates is None else [float(x) for x in learning_rates]
         if len(self.seeds) != P or len(lrs) != P or (rew_configs is not None and len(rew_configs) != P):
@@ -730,6 +749,8 @@ class PopulationPPO:
         (self.obs_buf, self.act_buf, self.logp_buf, self.val_buf, self.rew_buf, self.done_buf, self.adv_buf,
          self.ret_buf) = _rollout_buffers(T, n, od, dev)
         self.last_val = z(n)
+        if sample_order == "device":      # (persistent: a captured iteration writes it, the reductions read it afterwards)
+            self.stats = z(self.cfg.n_epochs * P * -(-T * epp // self.cfg.batch_size) * 8)
         self.step_base = torch.zeros(1, dtype=torch.int64, device=dev)
         self.act_lo, self.act_hi = float(env.action_space.low), float(env.action_space.high)
         if self._rollout(0) != 0:                         # T = 0: validates the configuration, launches nothing
@@ -782,23 +803,53 @@ class PopulationPPO:
         take the members' values from the table); afterwards one b747_policy_pack_batch.
         minibatch_order(epoch, T, envs_per_member, p) -> [T * envs_per_member] indices into MEMBER p's own time-major
         rows (t * envs_per_member + j: what PPO.train's hook gives a learner that has the member's envs to itself);
-        default torch.randperm.  Returns PPO.train's names as [P] tensors (float64; explained_variance and std
-        float32-derived), per member."""
-        T, c, P, epp = T or self.cfg.n_steps, self.cfg, self.n_members, self.envs_per_member
+        default torch.randperm.  With sample_order="device" the orders are one b747_ppo_sample_orders launch per epoch
+        (seed, step_base and the epoch key them; no hook).  Returns PPO.train's names as [P] tensors (float64;
+        explained_variance and std float32-derived), per member."""
+        T = T or self.cfg.n_steps
+        return self._train_stats(T, self._epochs(T, minibatch_order))
+
+    def _sample_orders(self, epoch: int, T: int, step_base: Optional[torch.Tensor]) -> int:
+        """One b747_ppo_sample_orders call into perm: every member's order of its T * envs_per_member rows for `epoch`;
+        the library's return code"""
+        dev = self.perm.device
+        return int(self._L.b747_ppo_sample_orders(
+            _p(self.perm), self.n_members, T, self.envs_per_member, self.env.n, self.seed & 0xFFFFFFFFFFFFFFFF,
+            None if step_base is None else _p(step_base), epoch,
+            torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None))
+
+    @torch.no_grad()
+    def _epochs(self, T: int, minibatch_order=None) -> torch.Tensor:
+        """train()'s device work: per epoch the sample orders and the epoch call, then the repack -- stream-ordered, and
+        with sample_order="device" free of host randomness, allocations and synchronisation (learn(use_graph=True)
+        captures it).  Returns the statistics [n_epochs, P, n_mb, 8] (with "device": a view of the persistent buffer)."""
+        c, P, epp = self.cfg, self.n_members, self.envs_per_member
         if self.env.n != P * epp:
             raise ValueError("PopulationPPO.train: every member needs envs_per_member envs (one n_rows for all members)")
+        device_order = self.sample_order == "device"
+        if device_order and minibatch_order is not None:
+            raise ValueError("PopulationPPO.train: minibatch_order with sample_order=\"device\" (the orders are "
+                             "b747_ppo_sample_orders'; build the population with sample_order=\"host\" to pass a hook)")
         dev, n_rows, p = self.env.device, T * epp, _p
         n_mb = -(-n_rows // c.batch_size)
-        rows_of = self.member_rows(T)
-        stats = torch.empty(c.n_epochs, P, n_mb, 8, dtype=torch.float32, device=dev)
+        if device_order:
+            assert T <= c.n_steps
+            stats = self.stats[:c.n_epochs * P * n_mb * 8].view(c.n_epochs, P, n_mb, 8)
+        else:
+            rows_of = self.member_rows(T)
+            stats = torch.empty(c.n_epochs, P, n_mb, 8, dtype=torch.float32, device=dev)
         for epoch in range(c.n_epochs):
-            if minibatch_order is None:
-                local = torch.stack([torch.randperm(n_rows, device=dev) for _ in range(P)])
+            if device_order:
+                self._lib.check(self._sample_orders(epoch, T, self.step_base), "b747_ppo_sample_orders")
+                perm = self.perm          # (its first P * n_rows entries: [P][n_rows], rows t * N + i of the buffers)
             else:
-                local = torch.stack([torch.as_tensor(minibatch_order(epoch, T, epp, m), device=dev).to(torch.int64)
-                                     for m in range(P)])
-            assert tuple(local.shape) == (P, n_rows), "minibatch_order must give every row of the member once"
-            perm = torch.gather(rows_of, 1, local).contiguous()       # member rows -> rows t * N + i of the buffers
+                if minibatch_order is None:
+                    local = torch.stack([torch.randperm(n_rows, device=dev) for _ in range(P)])
+                else:
+                    local = torch.stack([torch.as_tensor(minibatch_order(epoch, T, epp, m), device=dev).to(torch.int64)
+                                         for m in range(P)])
+                assert tuple(local.shape) == (P, n_rows), "minibatch_order must give every row of the member once"
+                perm = torch.gather(rows_of, 1, local).contiguous()   # member rows -> rows t * N + i of the buffers
             if self.hyper is not None:
                 head = (p(self.flat), P, self.stride, self.env.obs_dim, p(self.obs_buf), p(self.act_buf),
                         p(self.logp_buf), p(self.adv_buf), p(self.ret_buf), p(perm), n_rows, c.batch_size)
@@ -826,6 +877,12 @@ class PopulationPPO:
                 p(self.upd_ws), p(self.upd_grad), p(self.upd_m), p(self.upd_v), p(self.upd_t), c.max_grad_norm, self._lr,
                 0.9, 0.999, 1e-5, p(stats[epoch]), torch.cuda.current_stream().cuda_stream), "b747_ppo_epoch_population")
         self.repack()
+        return stats
+
+    @torch.no_grad()
+    def _train_stats(self, T: int, stats: torch.Tensor) -> dict:
+        """train()'s return value from the epochs' statistics [n_epochs, P, n_mb, 8] and the rollout buffers"""
+        P, epp = self.n_members, self.envs_per_member
         st = stats.double()
         mean, last = st.mean(dim=(0, 2)), st[-1].mean(dim=1)          # [P, 8]: every minibatch / the last epoch's
         v = self.val_buf[:T].reshape(T, P, epp).permute(1, 0, 2).reshape(P, -1)
@@ -840,14 +897,60 @@ class PopulationPPO:
         self._lib.check(self._L.b747_policy_pack_batch(self.flat.data_ptr(), self.env.obs_dim, self.n_members, self.stride,
                                                        torch.cuda.current_stream().cuda_stream), "b747_policy_pack_batch")
 
-    def learn(self, iterations: int, n_steps: Optional[int] = None, minibatch_order=None):
+    def _iteration_graph_key(self, T: int):
+        """What a captured iteration baked in (PPO._graph_key): the step count, the env's C descriptor, configuration
+        and constants, and the kernel specialisation"""
+        env = self.env
+        return (T, env._batch(), bytes(env.cfg), bytes(env.consts), int(self._L.b747_get_specialization()))
+
+    def _replay_iteration(self, T: int) -> torch.Tensor:
+        """One iteration's device work -- rollout, GAE, n_epochs x (orders + epoch call), repack -- as one replay of a
+        HIP graph captured on one stream (a linear graph: every call is stream-ordered behind the one before), captured
+        when there is none for this key (the capture launches nothing; the first iteration is a replay too).  The
+        kernels read step_base, the hyper-parameter table, the learning rates, the parameters and the Adam state on the
+        device when they run: set_hyper and copy_member between replays are stream-ordered copies into buffers the
+        graph already addresses.  Returns the statistics (_epochs': a view of the persistent buffer)."""
+        key = self._iteration_graph_key(T)
+        if self._graph is None or self._graph_key != key:
+            s = torch.cuda.Stream(device=self.env.device)
+            s.wait_stream(torch.cuda.current_stream())
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=s), torch.no_grad():
+                self.collect_rollouts(T)
+                self.compute_gae(T)
+                stats = self._epochs(T)
+            self._graph, self._graph_key, self._graph_stats = g, key, stats
+        self._graph.replay()
+        return self._graph_stats
+
+    def learn(self, iterations: int, n_steps: Optional[int] = None, minibatch_order=None, use_graph: bool = False):
+        """`iterations` x (collect_rollouts, compute_gae, train) after an env reset; train()'s values per iteration, with
+        mean_reward.  use_graph=True (needs sample_order="device" and batched_update=True: the other epoch calls take
+        the learning rates or the table from the host, which a capture would freeze) replays each iteration's device
+        work as one HIP graph (_replay_iteration) and computes the statistics outside it, from the persistent
+        buffers; the same bits as use_graph=False."""
         T, P, epp = n_steps or self.cfg.n_steps, self.n_members, self.envs_per_member
+        if use_graph:
+            if self.sample_order != "device":
+                raise ValueError("PopulationPPO.learn(use_graph=True) needs sample_order=\"device\" (the host's "
+                                 "torch.randperm draws cannot be captured)")
+            if not self.batched_update:
+                raise ValueError("PopulationPPO.learn(use_graph=True) needs batched_update=True (the other epoch calls "
+                                 "read the learning rates or the hyper-parameter table on the host: a capture would "
+                                 "freeze them)")
+        if minibatch_order is not None and self.sample_order == "device":
+            raise ValueError("PopulationPPO.learn: minibatch_order with sample_order=\"device\" (the orders are "
+                             "b747_ppo_sample_orders')")
+        assert T <= self.cfg.n_steps
         self.env.reset()
         hist = []
         for _ in range(iterations):
-            self.collect_rollouts(T)
-            self.compute_gae(T)
-            st = self.train(T, minibatch_order)
+            if use_graph:
+                st = self._train_stats(T, self._replay_iteration(T))
+            else:
+                self.collect_rollouts(T)
+                self.compute_gae(T)
+                st = self.train(T, minibatch_order)
             st["mean_reward"] = self.rew_buf[:T].reshape(T, P, epp).mean(dim=(0, 2))
             hist.append(st)
         return hist

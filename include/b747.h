@@ -40,7 +40,8 @@ extern "C" {
                                 * b747_ppo_epoch, b747_get_specialization; 14: + b747_ppo_rollout_lanes; 15: + b747_eval_population,
                                 * b747_policy_pack_batch.  b747_ppo_rollout_population, b747_ppo_epoch_population,
                                 * b747_ppo_epoch_batched_workspace and b747_ppo_epoch_batched, then
-                                * b747_ppo_gae_population, b747_ppo_epoch_population_hyper and b747_ppo_epoch_batched_hyper
+                                * b747_ppo_gae_population, b747_ppo_epoch_population_hyper and b747_ppo_epoch_batched_hyper,
+                                * then b747_ppo_sample_orders
                                 * came later as purely additive entry points under 15 (no struct, argument or
                                 * behaviour of an existing one changed): a library built before them still reports
                                 * 15, and a binding catches it by the missing entry point (_lib.bind) */
@@ -598,6 +599,28 @@ int32_t b747_ppo_gae_population(const float *rew, const float *val, const uint8_
                                 int32_t T, int64_t N, int32_t n_policies, int32_t envs_per_policy,
                                 const double *hyper_dev /* device, [n_policies][8] */, float *adv, float *ret,
                                 void *stream);
+
+/* ---- the minibatch sample orders of a population, drawn on the device (additive under ABI 15; DESIGN.md 18;
+ * PopulationPPO(sample_order="device")) ----
+ * Row perm[p] receives a uniformly drawn order of member p's n_rows = T * envs_per_policy rollout rows, as the global
+ * row numbers t * N + p * envs_per_policy + j that b747_ppo_epoch_population and its siblings read.  The order is fixed
+ * by this definition, not by the kernel: local row l = t * envs_per_policy + j gets the 32-bit word u(p, l), word l & 3
+ * of the Philox4x32-10 block (the rounds of the reset draws and the action noise) with
+ *   sb  = step_base ? *step_base : 0                          (read on the device, when the kernel runs)
+ *   K   = (seed ^ 0x6F72646572733A31) ^ ((sb >> 32) * 0x9E3779B97F4A7C15),   key (lo32(K), hi32(K))
+ *   ctr = (l >> 2, p, lo32(sb), epoch)
+ * and the rows are written in ascending order of the 64-bit key (u << 32) | l: a stable argsort of u, ties broken by l.
+ * The tag in K keeps the stream apart from the action noise (key seed ^ (ctr >> 32) * C) and the reset draws.
+ * b747_ppo_rollout_population advances *step_base, so a captured call replayed after every rollout draws fresh orders;
+ * `epoch` tells an iteration's epochs apart.  One workgroup per member sorts the keys in LDS (bitonic, 8 bytes per key,
+ * padded to a power of two): n_rows <= 16384 (128 KiB of the CU's 160) is the limit of this entry point.
+ * -hipErrorInvalidValue before anything reaches the device (b747_last_error names the argument) for perm == NULL,
+ * n_policies < 1, T < 0, envs_per_policy not a positive multiple of 64, n_policies * envs_per_policy > N, or
+ * T * envs_per_policy > 16384; T == 0 returns 0 and launches nothing.  Stream-ordered, graph-capturable, allocates
+ * nothing, synchronises nothing, reads nothing back. */
+int32_t b747_ppo_sample_orders(int64_t *perm /* device, [n_policies][T * envs_per_policy] */, int32_t n_policies,
+                               int32_t T, int32_t envs_per_policy, int64_t N, uint64_t seed,
+                               const uint64_t *step_base /* device, nullable: 0 */, uint32_t epoch, void *stream);
 
 /* Human-readable text of the last error returned on this thread. */
 const char *b747_last_error(void);
