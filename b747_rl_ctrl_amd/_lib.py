@@ -112,6 +112,9 @@ SIGNATURES = {
                                      + [_F64, _F64, _F64, _V, _V], _I32),
     # (the population's sample orders drawn on the device: perm, n_policies, T, envs_per_policy, N, seed, step_base, epoch)
     "b747_ppo_sample_orders": ([_V, _I32, _I32, _I32, _I64, _U64, _V, _U32, _V], _I32),
+    # (ControlTestCallback on the device: eval_out, n_eval, vref, tk, n_members, envs_per_policy, n_refs, window, repeat,
+    #  params, stride, then the caller-owned state ring, count, last, window_mean, best_quality, best_eval, best_params)
+    "b747_ppo_track_best": ([_V, _I64, _V, _F64, _I32, _I32, _I32, _I32, _I32, _V, _I64] + [_V] * 7 + [_V], _I32),
 }
 
 

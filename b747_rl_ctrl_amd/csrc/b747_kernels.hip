@@ -30,6 +30,7 @@
 #include "b747_ppo_update.h"
 #include "b747_ppo_gae.h"
 #include "b747_ppo_order.h"
+#include "b747_ppo_track.h"
 
 using namespace b747;
 
@@ -497,6 +498,35 @@ B747_API int32_t b747_ppo_sample_orders(int64_t *perm, int32_t n_policies, int32
     if (T == 0) return 0;
     return launched(W, launch_ppo_sample_orders(perm, n_policies, T, envs_per_policy, N, seed, step_base, epoch,
                                                 (hipStream_t)stream));
+}
+
+B747_API int32_t b747_ppo_track_best(const double *eval_out, int64_t n_eval, const double *vref, double tk,
+                                     int32_t n_members, int32_t envs_per_policy, int32_t n_refs, int32_t window,
+                                     int32_t repeat, const float *params, int64_t stride, double *ring, int64_t *count,
+                                     double *last, double *window_mean, double *best_quality, int64_t *best_eval,
+                                     float *best_params, void *stream)
+{
+    const char *const W = "b747_ppo_track_best";
+    if (int32_t e = check_not_null(W, {{eval_out, "eval_out"}, {vref, "vref"}, {params, "params"}, {ring, "ring"},
+                                       {count, "count"}, {last, "last"}, {window_mean, "window_mean"},
+                                       {best_quality, "best_quality"}, {best_eval, "best_eval"},
+                                       {best_params, "best_params"}}))
+        return e;
+    if (n_members < 1) return bad_arg(W, "n_members < 1");
+    if (envs_per_policy < 64 || envs_per_policy % 64 != 0)
+        return bad_arg(W, "envs_per_policy (a positive multiple of 64: the evaluation flies one policy per wave)");
+    if (n_refs < 1 || n_refs > envs_per_policy) return bad_arg(W, "n_refs (outside [1, envs_per_policy])");
+    if (n_eval < (int64_t)(n_members - 1) * envs_per_policy + n_refs || n_eval > (int64_t)n_members * envs_per_policy)
+        return bad_arg(W, "n_eval (outside ((n_members - 1) * envs_per_policy + n_refs - 1, n_members * envs_per_policy])");
+    if (window < 1 || window > kTrackMaxWindow)
+        return bad_arg(W, "window (outside [1, 128]: NumPy's summation order is kept up to 128 values)");
+    if (repeat < 1 || repeat > kTrackMaxRepeat) return bad_arg(W, "repeat (outside [1, 256])");
+    if (stride < 4 || stride % 4 != 0)
+        return bad_arg(W, "stride (at least 4 floats and a multiple of 4: the snapshot is copied 16 bytes at a time)");
+    if (!(tk > 0.0)) return bad_arg(W, "tk (not above 0)");
+    const TrackArgs a{eval_out, vref, params, ring, count, last, window_mean, best_quality, best_eval, best_params,
+                      n_eval, stride, tk, n_members, envs_per_policy, n_refs, window, repeat};
+    return launched(W, launch_ppo_track_best(a, (hipStream_t)stream));
 }
 
 B747_API int32_t b747_ppo_epoch(float *theta, int32_t obs_dim, const float *obs, const float *act, const float *old_logp,

@@ -376,9 +376,17 @@ class BatchControllerEnv:
                                             ptr(done_seq), s.cuda_stream), "b747_env_rollout")
         return self.obs, self.reward, self.done
 
+    def _eval_out(self, out: Optional[torch.Tensor]) -> torch.Tensor:
+        """The [B747_NEVAL, N] float64 buffer an evaluation writes: the caller's `out` where given, else a fresh one"""
+        if out is None:
+            return torch.empty(len(_lib.EVAL_ROWS), self.n, dtype=torch.float64, device=self.device)
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.device == self.device \
+            and tuple(out.shape) == (len(_lib.EVAL_ROWS), self.n), "out: [7, N] contiguous float64 on the env's device"
+        return out
+
     def eval_episodes(self, n_env_steps: int, params: Optional[torch.Tensor] = None, signal: str = "state_vartheta",
                       scale: float = 1.0, y_base=None, error_band: float = 0.05, action=None, act_lo: float = None,
-                      act_hi: float = None, stream=None):
+                      act_hi: float = None, stream=None, out: Optional[torch.Tensor] = None):
         """One whole episode per env in ONE launch (b747_eval_episodes, include/b747.h): up to n_env_steps env
         steps from the current state, each env ending at its first done (the env needs auto_reset=False), with
         the reference's calc_stepinfo of `scale * nan_to_num(signal)` against y_base [N] accumulated inside the
@@ -387,7 +395,9 @@ class BatchControllerEnv:
         act_hi] (default: the action space).  params None: `action` [N] (default 0) is held for the whole episode
         -- ignored where the SS PID flies (AUTO / FULL_AUTO).  y_base defaults to scale * the constant pitch
         reference.  Returns {"overshoot" (signed %), "rise_time", "settling_time", "static_error", "itse",
-        "length" (DLL steps), "return"}: [N] float64 tensors."""
+        "length" (DLL steps), "return"}: [N] float64 tensors.  out (optional): the caller's own [7, N] float64 buffer
+        for them on the env's device, written in place of a fresh one; with it, a contiguous float64 [N] y_base on the
+        device is read where it lies, and the call allocates nothing."""
         from .model import SIG
         s = torch.cuda.current_stream(self.device) if stream is None else stream
         b = self._batch()
@@ -395,7 +405,7 @@ class BatchControllerEnv:
             yb = self.ref[0] * scale if y_base is None else \
                 torch.as_tensor(y_base, dtype=torch.float64, device=self.device).expand(self.n)
             yb = yb.to(torch.float64).contiguous()
-            out = torch.empty(len(_lib.EVAL_ROWS), self.n, dtype=torch.float64, device=self.device)
+            out = self._eval_out(out)
             if params is None:
                 if action is None:
                     self.action.zero_()
@@ -417,12 +427,13 @@ class BatchControllerEnv:
 
     def eval_population(self, n_env_steps: int, params: Optional[torch.Tensor] = None, envs_per_policy: int = 64,
                         pid_ss=None, pid_cs=None, signal: str = "state_vartheta", scale: float = 1.0, y_base=None,
-                        error_band: float = 0.05, action=None, act_lo: float = None, act_hi: float = None, stream=None):
+                        error_band: float = 0.05, action=None, act_lo: float = None, act_hi: float = None, stream=None,
+                        out: Optional[torch.Tensor] = None):
         """eval_episodes with a policy per group of envs and PID gains per env, still ONE launch
         (b747_eval_population, include/b747.h).  params [P, stride]: packed policies (evaluate.pack_policies); policy p
         flies envs [p * envs_per_policy, (p + 1) * envs_per_policy) (a multiple of 64; the last group may be partial).
         pid_ss / pid_cs [N, 4] (or [4] for every env; None = the batch's consts): env i's own SS / CS PID gains.  The
-        remaining arguments and the returned dict are eval_episodes'."""
+        remaining arguments (out and y_base among them) and the returned dict are eval_episodes'."""
         from .model import SIG
         s = torch.cuda.current_stream(self.device) if stream is None else stream
         b = self._batch()
@@ -430,7 +441,7 @@ class BatchControllerEnv:
             yb = self.ref[0] * scale if y_base is None else \
                 torch.as_tensor(y_base, dtype=torch.float64, device=self.device).expand(self.n)
             yb = yb.to(torch.float64).contiguous()
-            out = torch.empty(len(_lib.EVAL_ROWS), self.n, dtype=torch.float64, device=self.device)
+            out = self._eval_out(out)
             gains = []
             for g in (pid_ss, pid_cs):           # [N, 4] -> the kernel's [4][N]
                 if g is not None:

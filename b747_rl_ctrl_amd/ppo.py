@@ -309,6 +309,7 @@ class PPO:
         self.noise = z(n, 1)
         self._graph = None
         self._graph_steps = 0
+        self.control_test = None          # learn()'s default for its control_test keyword
         if self.fused:
             from . import _lib
             self._lib = _lib
@@ -619,15 +620,27 @@ class PPO:
             1e-5, p(rows), torch.cuda.current_stream().cuda_stream), "b747_ppo_epoch")
         return rows[-1, 7]
 
-    def learn(self, iterations: int, n_steps: Optional[int] = None):
+    def learn(self, iterations: int, n_steps: Optional[int] = None, control_test=None):
+        """`iterations` x (collect_rollouts, compute_gae, train) after an env reset; train()'s values per iteration, with
+        mean_reward.  control_test (a ControlTest built for this learner; None = self.control_test, and with that None
+        too today's calls, bits and keys): before
+        an iteration's device work it flies the step tests with the policy the rollout is about to use, as often as the
+        reference's callback would during that rollout (control_test_pushes), and the iteration's entry gains
+        transfer_settling_time / transfer_overshoot / transfer_quality, [1] device tensors."""
         T = n_steps or self.cfg.n_steps
+        control_test = self.control_test if control_test is None else control_test
+        pushes = _control_test_plan(self, control_test, iterations, T)
         self.last_obs.copy_(self.env.reset())
         self._last_obs_from_env = False
         hist = []
-        for _ in range(iterations):
+        for it in range(iterations):
+            if pushes is not None and pushes[it]:
+                control_test.evaluate(pushes[it])
             self.collect_rollouts(T)
             self.compute_gae(T)
             hist.append(self.train(T) | {"mean_reward": float(self.rew_buf[:T].mean())})
+            if pushes is not None:
+                hist[-1].update(control_test.history_entry())
         return hist
 
     def step_tests(self, vartheta_ref, state0=(0, 11000, 250, 0, 0, 0), tk: Optional[float] = None, **kwargs):
@@ -652,7 +665,7 @@ class PopulationPPO:
     learning rate; gamma, gae_lambda, the clip range, the epochs and the batch size (rows of ONE member per minibatch) are
     cfg's, shared (the first three and the loss coefficients per member with `hyper`, below).  This is the shape of the reference's ControllerAgent.optimize() (neural/agent.py:89-136): trials
     that differ in reward_config and hyper-parameters, ranked by ControlTestCallback.mean_quality -- step_tests()
-    here.  The update is PPO(fused_update=True, epoch_call=True)'s, per member, from one C call per epoch
+    here; ControlTest (below) keeps that callback's windows, its best quality and its saved model on the device.  The update is PPO(fused_update=True, epoch_call=True)'s, per member, from one C call per epoch
     (b747_ppo_epoch_population): the same kernels, the same bits as P separate learners
     (tests/test_gpu_ppo_population_train.py).  `seed` keys the action noise (Philox counters (seed, step, global env
     id), shared by the members, whose env ids differ).  No torch modules are kept: `flat` [P, stride] is the master copy
@@ -702,6 +715,7 @@ class PopulationPPO:
             raise ValueError(f"PopulationPPO: sample_order={sample_order!r}: \"host\" or \"device\"")
         self.sample_order = sample_order
         self._graph, self._graph_key = None, None
+        self.control_test = None          # a ControlTest that learn() flies and books before every iteration
         if sample_order == "device":
             # the persistent order buffer, and the first draw into it (epoch 0 at step_base 0; train() draws again): the
             # entry point refuses a member of more rows than it sorts, or envs that the members do not cover, before
@@ -928,8 +942,18 @@ class PopulationPPO:
         mean_reward.  use_graph=True (needs sample_order="device" and batched_update=True: the other epoch calls take
         the learning rates or the table from the host, which a capture would freeze) replays each iteration's device
         work as one HIP graph (_replay_iteration) and computes the statistics outside it, from the persistent
-        buffers; the same bits as use_graph=False."""
+        buffers; the same bits as use_graph=False.
+        self.control_test (a ControlTest built for this population, attached as `pop.control_test = ControlTest(pop,
+        ...)`; None, the default = today's calls, bits and keys; an attribute, not a keyword as PPO.learn
+        has it: this method's parameter list is pinned by tests/test_ppo_sample_orders_abi.py):
+        before an iteration's device work -- outside the captured iteration, before its replay -- it flies the step
+        tests with the policies the rollout is about to use and books them as often as the reference's callback would
+        evaluate during that rollout (control_test_pushes; none launches nothing, more than 256 is a ValueError here).
+        The iteration's entry gains transfer_settling_time / transfer_overshoot / transfer_quality: [P] device clones of
+        the windowed means after those pushes, NaN until the first evaluation."""
         T, P, epp = n_steps or self.cfg.n_steps, self.n_members, self.envs_per_member
+        control_test = self.control_test
+        pushes = _control_test_plan(self, control_test, iterations, T)
         if use_graph:
             if self.sample_order != "device":
                 raise ValueError("PopulationPPO.learn(use_graph=True) needs sample_order=\"device\" (the host's "
@@ -944,7 +968,9 @@ class PopulationPPO:
         assert T <= self.cfg.n_steps
         self.env.reset()
         hist = []
-        for _ in range(iterations):
+        for it in range(iterations):
+            if pushes is not None and pushes[it]:
+                control_test.evaluate(pushes[it])
             if use_graph:
                 st = self._train_stats(T, self._replay_iteration(T))
             else:
@@ -952,6 +978,8 @@ class PopulationPPO:
                 self.compute_gae(T)
                 st = self.train(T, minibatch_order)
             st["mean_reward"] = self.rew_buf[:T].reshape(T, P, epp).mean(dim=(0, 2))
+            if pushes is not None:
+                st.update(control_test.history_entry())
             hist.append(st)
         return hist
 
@@ -1010,3 +1038,152 @@ class PopulationPPO:
         e = self.env
         kw = _step_test_kwargs(e) | kwargs
         return population_step_tests(self.flat, vartheta_ref, state0=state0, tk=e.tk if tk is None else tk, **kw)
+
+
+def control_test_pushes(iterations: int, T: int, log_interval: int) -> list:
+    """How often iteration it = 0 .. iterations - 1 of T rollout steps makes the reference's ControlTestCallback fly
+    its step tests: (it + 1) * T // L - it * T // L, the multiples of L = log_interval among the callback's n_calls
+    it * T + 1 .. (it + 1) * T (neural/callbacks.py:106).  ValueError for more than 256 in one iteration
+    (b747_ppo_track_best's limit on one call's pushes)."""
+    T, L = int(T), int(log_interval)
+    if T < 1 or L < 1:
+        raise ValueError(f"control_test_pushes: {T} rollout steps, log_interval {L} (both at least 1)")
+    ms = [(it + 1) * T // L - it * T // L for it in range(int(iterations))]
+    if ms and max(ms) > 256:
+        raise ValueError(f"learn(control_test=...): {max(ms)} evaluations in one iteration ({T} rollout steps at "
+                         f"log_interval {L}); b747_ppo_track_best takes at most 256 pushes a call -- raise log_interval")
+    return ms
+
+
+class ControlTest:
+    """The reference's ControlTestCallback (neural/callbacks.py:46-120) kept on the device, for a PopulationPPO or a
+    PPO(fused=True) (handled as one member, its `flat` seen as [1, stride]); DESIGN.md 19.
+
+    The callback flies the step tests with the current deterministic policy every log_interval calls, appends the means
+    over the references to three windows of the last window_length evaluations, logs the windowed means as
+    transfer_custom/* and saves the model whenever the windowed mean quality beats the best so far; optimize() ranks a
+    trial by that windowed quality and reloads the saved model (neural/agent.py:115-133).  Here evaluate() is a reset of
+    ONE persistent test env, one evaluation launch that reads the learner's packed `flat` where it lies
+    (b747_eval_population; b747_eval_episodes for a PPO) and one b747_ppo_track_best launch that keeps the books for
+    every member: no host read, no synchronisation and no allocation after construction, so learn(control_test=...)
+    stays free of host reads.
+
+    The test env is population_step_tests' (PPO.step_tests' for a PPO): (P - 1) * 64 + R envs, the references repeated
+    per 64-env group, the learner's env settings (_step_test_kwargs) overridden by env_kwargs (e.g. aero_err for
+    main.py's test env), auto_reset off, tk the learner env's unless given.  State, all on the device: eval_out [7, n]
+    (the last evaluation's per-env metrics), ring [3, P, W], count [P], last and window_mean [P, 3] (settling_time,
+    overshoot, quality; NaN until the first evaluation), best_quality [P] (0 at first, as the callback's), best_eval [P]
+    (the push that saved last; -1: nothing saved yet) and best_flat [P, stride] (a copy of the learner's flat at
+    construction, so that it always holds a flyable policy)."""
+
+    def __init__(self, learner, vartheta_ref, state0=(0, 11000, 250, 0, 0, 0), log_interval: int = 1000,
+                 window_length: int = 30, tk: Optional[float] = None, **env_kwargs):
+        from .ctrl_env import CtrlType
+        refs = [float(v) for v in vartheta_ref] if isinstance(vartheta_ref, (list, tuple)) else [float(vartheta_ref)]
+        R, W, L = len(refs), int(window_length), int(log_interval)
+        if not 1 <= R <= 64:
+            raise ValueError(f"ControlTest: {R} references (1 .. 64: one 64-env group per member)")
+        if not 1 <= W <= 128:
+            raise ValueError(f"ControlTest: window_length={W} (1 .. 128: b747_ppo_track_best keeps NumPy's summation "
+                             "order up to 128 values)")
+        if L < 1:
+            raise ValueError(f"ControlTest: log_interval={L} (at least 1)")
+        population = isinstance(learner, PopulationPPO)
+        if not population and not (isinstance(learner, PPO) and learner.fused):
+            raise ValueError("ControlTest: the learner is a PopulationPPO or a PPO(fused=True) (the evaluation reads "
+                             "the packed parameter buffer `flat`)")
+        self.learner, self.population = learner, population
+        self.vartheta_ref, self.log_interval, self.window_length = refs, L, W
+        P = learner.n_members if population else 1
+        self.n_members, self.n_refs = P, R
+        e = learner.env
+        if e.obs_dim not in (3, 5):
+            raise ValueError("ControlTest: the evaluation kernel runs a policy with a PID_LIKE or SPEED_MODE observation")
+        kw = _step_test_kwargs(e) | env_kwargs
+        kw["auto_reset"] = False
+        ctrl_type = kw.pop("ctrl_type", CtrlType.MANUAL)
+        self.tk = float(e.tk if tk is None else tk)
+        dev, f64 = e.device, torch.float64
+        n = (P - 1) * 64 + R
+        env = BatchControllerEnv(n, kw.pop("observation_type"), kw.pop("reward_type"), kw.pop("norm_obs"),
+                                 kw.pop("norm_act"), ctrl_type, kw.pop("ctrl_mode"), reset_ref_mode=None, tk=self.tk, **kw)
+        env.set_state0(torch.tensor(state0, dtype=f64))
+        env.set_reference(vartheta=torch.tensor((refs * 64)[:64] * P, dtype=f64, device=dev)[:n])
+        self.env = env
+        self.steps = int(math.ceil(self.tk / env.sample_time - 1e-9))
+        self.vref = env.ref[0].to(f64).clone()
+        self.y_base = self.vref * 180 / math.pi          # (the step tests' expression: the same bits)
+        self.stride = int(learner.flat.numel() // P)
+        self.eval_out = torch.zeros(len(learner._lib.EVAL_ROWS), n, dtype=f64, device=dev)
+        nan = lambda *s: torch.full(s, math.nan, dtype=f64, device=dev)
+        self.ring, self.last, self.window_mean = nan(3, P, W), nan(P, 3), nan(P, 3)
+        self.count = torch.zeros(P, dtype=torch.int64, device=dev)
+        self.best_quality = torch.zeros(P, dtype=f64, device=dev)
+        self.best_eval = torch.full((P,), -1, dtype=torch.int64, device=dev)
+        self.best_flat = learner.flat.detach().reshape(P, self.stride).clone()
+        self.evaluations = 0          # evaluate() calls so far (host side; the device's count is pushes)
+
+    def _reset_test_env(self):
+        """The test env back to what a freshly built one is before its evaluation.  b747_env_reset leaves three things
+        behind that the evaluation reads: the episode counter (it keys the reset's disturbance draws; a fresh env
+        evaluates its episode 1), and tp and h_zh, which a reset does not rewrite (the TF_REFERENCE reward and the CS
+        loop read them).  Three fills and the reset, all stream-ordered."""
+        env = self.env
+        env.episode.fill_(1)
+        env.tp.zero_()
+        env.h_zh.fill_(11000.0)
+        env.reset()
+
+    @torch.no_grad()
+    def evaluate(self, repeat: int = 1):
+        """One callback evaluation of the learner's current policies, booked `repeat` times (1 .. 256): the test env's
+        reset, the evaluation launch on the learner's `flat` itself (packed after every update) and
+        b747_ppo_track_best, on the current stream."""
+        repeat = int(repeat)
+        if not 1 <= repeat <= 256:
+            raise ValueError(f"ControlTest.evaluate: repeat={repeat} (1 .. 256)")
+        lr, env, p = self.learner, self.env, _p
+        self._reset_test_env()
+        if self.population:
+            env.eval_population(self.steps, lr.flat, 64, signal="state_vartheta", scale=180 / math.pi,
+                                y_base=self.y_base, out=self.eval_out)
+        else:
+            env.eval_episodes(self.steps, lr.flat, "state_vartheta", scale=180 / math.pi, y_base=self.y_base,
+                              out=self.eval_out)
+        lr._lib.check(lr._L.b747_ppo_track_best(
+            p(self.eval_out), env.n, p(self.vref), self.tk, self.n_members, 64, self.n_refs, self.window_length, repeat,
+            p(lr.flat), self.stride, p(self.ring), p(self.count), p(self.last), p(self.window_mean),
+            p(self.best_quality), p(self.best_eval), p(self.best_flat), torch.cuda.current_stream().cuda_stream),
+            "b747_ppo_track_best")
+        self.evaluations += 1
+
+    def history_entry(self) -> dict:
+        """The callback's transfer_custom/* log values: [P] device clones of the windowed means (NaN before the first
+        evaluation)"""
+        wm = self.window_mean
+        return {"transfer_settling_time": wm[:, 0].clone(), "transfer_overshoot": wm[:, 1].clone(),
+                "transfer_quality": wm[:, 2].clone()}
+
+    def objective(self) -> torch.Tensor:
+        """[P] the windowed mean quality: what optimize()'s objective returns for a trial (neural/agent.py:131)"""
+        return self.window_mean[:, 2]
+
+    def best_member(self) -> torch.Tensor:
+        """The member whose saved model reached the highest windowed quality (a device scalar)"""
+        return self.best_quality.argmax()
+
+    def best(self, p: int = 0) -> ActorCritic:
+        """Member p's saved model (the callback's best_model file) as an ActorCritic on the learner's device; before the
+        first save, the policy the member started with"""
+        net = ActorCritic(self.learner.env.obs_dim).to(self.learner.env.device)
+        load_flat(net, self.best_flat[int(p)])
+        return net
+
+
+def _control_test_plan(learner, control_test, iterations: int, T: int):
+    """learn()'s pushes per iteration for its control_test (None: no evaluations)"""
+    if control_test is None:
+        return None
+    if getattr(control_test, "learner", None) is not learner:
+        raise ValueError("learn(control_test=...): the ControlTest was built for another learner")
+    return control_test_pushes(iterations, T, control_test.log_interval)

@@ -41,7 +41,7 @@ extern "C" {
                                 * b747_policy_pack_batch.  b747_ppo_rollout_population, b747_ppo_epoch_population,
                                 * b747_ppo_epoch_batched_workspace and b747_ppo_epoch_batched, then
                                 * b747_ppo_gae_population, b747_ppo_epoch_population_hyper and b747_ppo_epoch_batched_hyper,
-                                * then b747_ppo_sample_orders
+                                * then b747_ppo_sample_orders, then b747_ppo_track_best
                                 * came later as purely additive entry points under 15 (no struct, argument or
                                 * behaviour of an existing one changed): a library built before them still reports
                                 * 15, and a binding catches it by the missing entry point (_lib.bind) */
@@ -621,6 +621,44 @@ int32_t b747_ppo_gae_population(const float *rew, const float *val, const uint8_
 int32_t b747_ppo_sample_orders(int64_t *perm /* device, [n_policies][T * envs_per_policy] */, int32_t n_policies,
                                int32_t T, int32_t envs_per_policy, int64_t N, uint64_t seed,
                                const uint64_t *step_base /* device, nullable: 0 */, uint32_t epoch, void *stream);
+
+/* ---- the reference's ControlTestCallback kept on the device (additive under ABI 15; DESIGN.md 19;
+ * ppo.ControlTest) ----
+ * One call books ONE step-test evaluation of a population -- what b747_eval_population / b747_eval_episodes left in
+ * eval_out -- `repeat` times, as neural/callbacks.py:90-119 does per callback call.  Member p's reported envs are
+ * p * envs_per_policy + [0, n_refs).  Per member, in float64:
+ *   per env     settling_time, |overshoot| and quality = exp(-60 * 0.1 * itse / (tk * (vref * vref))), evaluated in
+ *               that order (Controller.quality, core/controller.py:336)
+ *   last[p]     the mean of each over the n_refs envs: (settling_time, overshoot, quality)
+ *   repeat x    push last[p] into ring[.][p][count[p] % window], ++count[p]; window_mean[p] = the mean of the
+ *               min(count[p], window) newest entries, oldest first; if window_mean[p].quality > best_quality[p] (strict:
+ *               a NaN never saves) best_quality[p] = it, best_eval[p] = the index of this push (count[p] - 1), and the
+ *               member is marked
+ *   save        a marked member's row params[p] is copied to best_params[p] once, after the pushes (16-byte loads and
+ *               stores by the whole workgroup; both rows 16-byte aligned); no other row is touched
+ * Every mean is taken in the order of NumPy's np.mean of a list of n <= 128 values a: sequentially from 0 for n < 8;
+ * otherwise r[j] = a[j] (j < 8), r[j] += a[i + j] for i = 8, 16, .. < n - n % 8, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) +
+ * (r6 + r7)), the last n % 8 values added in order; divided by n.  Given the same last[p] the windows, the decisions
+ * and the snapshots are therefore the callback's exactly; last[p].quality itself differs from NumPy's by the two
+ * libraries' exp (about 1 ulp each).  More than 128 references are summed in the same eight-sum order (NumPy would
+ * split the range there).
+ * The state is the caller's, device memory, read and rewritten by every call: ring [3][n_members][window] (metric-major),
+ * count [n_members] (pushes so far), last and window_mean [n_members][3], best_quality [n_members], best_eval
+ * [n_members] (-1: nothing saved yet), best_params [n_members][stride].  A fresh tracker has count 0, best_quality 0 and
+ * best_eval -1; ring, last and window_mean need no initial value.
+ * One workgroup per member; one lane per metric keeps the books in an LDS copy of the member's windows.  No atomics:
+ * the same inputs give the same bits.  -hipErrorInvalidValue before anything reaches the device (b747_last_error names
+ * the argument) for a NULL pointer, n_members < 1, envs_per_policy not a positive multiple of 64, n_refs outside
+ * [1, envs_per_policy], n_eval outside ((n_members - 1) * envs_per_policy + n_refs - 1, n_members * envs_per_policy],
+ * window outside [1, 128], repeat outside [1, 256], stride < 4 or not a multiple of 4, or tk not above 0.
+ * Stream-ordered, graph-capturable, allocates nothing, synchronises nothing, reads nothing back. */
+int32_t b747_ppo_track_best(const double *eval_out /* device, [B747_NEVAL][n_eval] */, int64_t n_eval,
+                            const double *vref /* device, [n_eval], rad */, double tk, int32_t n_members,
+                            int32_t envs_per_policy, int32_t n_refs, int32_t window, int32_t repeat,
+                            const float *params /* device, [n_members][stride] */, int64_t stride,
+                            double *ring /* device, [3][n_members][window] */, int64_t *count, double *last,
+                            double *window_mean, double *best_quality, int64_t *best_eval,
+                            float *best_params /* device, [n_members][stride] */, void *stream);
 
 /* Human-readable text of the last error returned on this thread. */
 const char *b747_last_error(void);
