@@ -13,6 +13,7 @@ NX, NDISC, NSIG, NAERO = 18, 9, 31, 5
 EVAL_ROWS = ("overshoot", "rise_time", "settling_time", "static_error", "itse", "length", "return")   # B747_NEVAL
 F_PID_SS, F_PID_CS, F_RP, F_RL = 1, 2, 4, 8
 VARIANT_FAST, VARIANT_FAITHFUL, VARIANT_MIXED = 0, 1, 2
+OPT_ADAM, OPT_RMSPROP, OPT_RMSPROP_TF = 0, 1, 2        # B747_OPT_*: b747_a2c_update's optimizer
 
 
 class B747Error(RuntimeError):
@@ -115,6 +116,12 @@ SIGNATURES = {
     # (ControlTestCallback on the device: eval_out, n_eval, vref, tk, n_members, envs_per_policy, n_refs, window, repeat,
     #  params, stride, then the caller-owned state ring, count, last, window_mean, best_quality, best_eval, best_params)
     "b747_ppo_track_best": ([_V, _I64, _V, _F64, _I32, _I32, _I32, _I32, _I32, _V, _I64] + [_V] * 7 + [_V], _I32),
+    # (A2C: theta, obs_dim, obs, act, adv, ret, idx (may be None), batch, normalize_advantage, ent_coef, vf_coef, workspace,
+    #  grad, stats; RMSprop on the flat vector; both from one call: + optimizer, state0, state1, t, max_grad_norm, lr, alpha, eps)
+    "b747_a2c_grad": ([_V, _I32] + [_V] * 5 + [_I64, _I32, _F64, _F64, _V, _V, _V, _V], _I32),
+    "b747_ppo_rmsprop": ([_V, _V, _V, _V, _I64] + [_F64] * 5 + [_I32, _V], _I32),
+    "b747_a2c_update": ([_V, _I32] + [_V] * 5 + [_I64, _I32, _F64, _F64, _V, _V, _V, _I32, _V, _V, _V] + [_F64] * 4 + [_V],
+                        _I32),
 }
 
 

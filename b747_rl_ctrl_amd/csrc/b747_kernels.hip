@@ -28,6 +28,7 @@
 #include "b747_rollout_lanes.h"
 #define B747_PPO_UPDATE_NO_KERNELS   // the update kernels live in b747_ppo_update.hip; this unit calls their launchers
 #include "b747_ppo_update.h"
+#include "b747_a2c_update.h"
 #include "b747_ppo_gae.h"
 #include "b747_ppo_order.h"
 #include "b747_ppo_track.h"
@@ -165,6 +166,29 @@ int32_t check_upd_rows(const char *where, const UpdData &d, const int64_t *idx, 
             return bad_arg(where, "n_rows % batch_size == 1 (the last minibatch would be one row: no standard deviation)");
     }
     return check_not_null(where, {{workspace, "workspace"}});
+}
+
+// --- the A2C family (b747_a2c_grad, b747_ppo_rmsprop, b747_a2c_update), in two parts: the rows (idx may be NULL), the
+// optimiser's scalars (alpha: RMSprop's only)
+int32_t check_a2c_rows(const char *where, const float *theta, int32_t obs_dim, const UpdData &d, int64_t batch,
+                       int32_t normalize_advantage, const void *workspace, const float *grad, const float *stats)
+{
+    if (int32_t e = check_upd_policy(where, theta, obs_dim)) return e;
+    if (int32_t e = check_not_null(where, {{d.obs, "obs"}, {d.act, "act"}, {d.adv, "adv"}, {d.ret, "ret"}})) return e;
+    if (batch < 1) return bad_arg(where, "batch < 1");
+    if (normalize_advantage && batch < 2)
+        return bad_arg(where, "batch < 2 with normalize_advantage (the advantages' standard deviation needs two rows)");
+    return check_not_null(where, {{workspace, "workspace"}, {grad, "grad"}, {stats, "stats"}});
+}
+int32_t check_opt_scalars(const char *where, int64_t n_params, double max_grad_norm, double lr, double eps,
+                          bool rmsprop, double alpha)
+{
+    if (n_params < 1) return bad_arg(where, "n_params < 1");
+    if (!(isfinite(max_grad_norm) && max_grad_norm > 0.0)) return bad_arg(where, "max_grad_norm (not finite and above 0)");
+    if (!(isfinite(lr) && lr > 0.0)) return bad_arg(where, "lr (not finite and above 0)");
+    if (!(isfinite(eps) && eps > 0.0)) return bad_arg(where, "eps (not finite and above 0)");
+    if (rmsprop && !(alpha >= 0.0 && alpha < 1.0)) return bad_arg(where, "alpha (outside [0, 1))");
+    return 0;
 }
 
 // --- the population tiling (b747_eval_population, b747_ppo_rollout_population), in two parts: the groups, then -- once
@@ -442,6 +466,54 @@ B747_API int32_t b747_ppo_adam(float *theta, float *m, float *v, int64_t *t, con
     if (n_params < 1) return bad_arg("n_params < 1");
     return launched("b747_ppo_adam", launch_ppo_adam({theta, m, v, t}, grad, n_params, grad_scale,
                                                      {max_grad_norm, beta1, beta2, eps}, lr, (hipStream_t)stream));
+}
+
+B747_API int32_t b747_a2c_grad(const float *theta, int32_t obs_dim, const float *obs, const float *act, const float *adv,
+                               const float *ret, const int64_t *idx, int64_t batch, int32_t normalize_advantage,
+                               double ent_coef, double vf_coef, void *workspace, float *grad, float *stats, void *stream)
+{
+    const char *const W = "b747_a2c_grad";
+    const UpdData d{obs, act, nullptr, adv, ret};
+    if (int32_t e = check_a2c_rows(W, theta, obs_dim, d, batch, normalize_advantage, workspace, grad, stats)) return e;
+    return launched(W, launch_a2c_grad(theta, obs_dim, d, idx, batch, normalize_advantage != 0, ent_coef, vf_coef,
+                                       workspace, grad, stats, (hipStream_t)stream));
+}
+
+B747_API int32_t b747_ppo_rmsprop(float *theta, float *sq, int64_t *t, const float *grad, int64_t n_params,
+                                  double grad_scale, double max_grad_norm, double lr, double alpha, double eps,
+                                  int32_t tf_like, void *stream)
+{
+    const char *const W = "b747_ppo_rmsprop";
+    if (int32_t e = check_not_null(W, {{theta, "theta"}, {sq, "sq"}, {t, "t"}, {grad, "grad"}})) return e;
+    if (int32_t e = check_opt_scalars(W, n_params, max_grad_norm, lr, eps, true, alpha)) return e;
+    return launched(W, launch_ppo_rmsprop(theta, sq, t, grad, n_params, grad_scale,
+                                          {max_grad_norm, alpha, eps, tf_like != 0}, lr, (hipStream_t)stream));
+}
+
+B747_API int32_t b747_a2c_update(float *theta, int32_t obs_dim, const float *obs, const float *act, const float *adv,
+                                 const float *ret, const int64_t *idx, int64_t batch, int32_t normalize_advantage,
+                                 double ent_coef, double vf_coef, void *workspace, float *grad, float *stats,
+                                 int32_t optimizer, float *state0, float *state1, int64_t *t, double max_grad_norm,
+                                 double lr, double alpha, double eps, void *stream)
+{
+    const char *const W = "b747_a2c_update";
+    const UpdData d{obs, act, nullptr, adv, ret};
+    if (int32_t e = check_a2c_rows(W, theta, obs_dim, d, batch, normalize_advantage, workspace, grad, stats)) return e;
+    if (optimizer != B747_OPT_ADAM && optimizer != B747_OPT_RMSPROP && optimizer != B747_OPT_RMSPROP_TF)
+        return bad_arg(W, "optimizer (B747_OPT_ADAM, B747_OPT_RMSPROP or B747_OPT_RMSPROP_TF)");
+    const bool adam = optimizer == B747_OPT_ADAM;
+    if (int32_t e = check_not_null(W, {{state0, "state0"}, {adam ? state1 : state0, "state1"}, {t, "t"}})) return e;
+    const int64_t n_params = PolicyLayout::of(obs_dim).total;
+    if (int32_t e = check_opt_scalars(W, n_params, max_grad_norm, lr, eps, !adam, alpha)) return e;
+    const hipStream_t s = (hipStream_t)stream;
+    if (int32_t e = launched(W, launch_a2c_grad(theta, obs_dim, d, idx, batch, normalize_advantage != 0, ent_coef,
+                                                vf_coef, workspace, grad, stats, s)))
+        return e;
+    if (adam)
+        return launched(W, launch_ppo_adam({theta, state0, state1, t}, grad, n_params, 1.0,
+                                           {max_grad_norm, 0.9, 0.999, eps}, lr, s));
+    return launched(W, launch_ppo_rmsprop(theta, state0, t, grad, n_params, 1.0,
+                                          {max_grad_norm, alpha, eps, optimizer == B747_OPT_RMSPROP_TF}, lr, s));
 }
 
 B747_API int32_t b747_ppo_gae(const float *rew, const float *val, const uint8_t *done, const float *last_value,

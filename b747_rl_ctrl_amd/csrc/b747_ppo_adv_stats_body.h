@@ -7,10 +7,10 @@
         part = reinterpret_cast<double *>(reinterpret_cast<char *>(part) + (int64_t)blockIdx.y * pa.ws_stride);
     }
     __shared__ double red[2][256];
-    const double x0 = (double)adv[idx[0]];
+    const double x0 = (double)adv[upd_row<LOSS>(idx, 0)];
     double s = 0.0, q = 0.0;
     for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < batch; j += (int64_t)gridDim.x * 256) {
-        const double d = (double)adv[idx[j]] - x0;
+        const double d = (double)adv[upd_row<LOSS>(idx, j)] - x0;
         s += d;
         q += d * d;
     }

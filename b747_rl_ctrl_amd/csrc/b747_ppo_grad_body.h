@@ -1,6 +1,7 @@
 // b747_ppo_grad_body.h -- the body of k_ppo_grad<OD> and of its member-batched sibling k_pop_grad<OD>
 // (b747_ppo_update.h).  Textual, not an inlined function, as b747_eval_body.h: the existing kernels keep their
-// instruction streams.  In scope where it is included: OD, POP, the arguments of k_ppo_grad and pa (read with POP only).
+// instruction streams.  In scope where it is included: OD, POP, LOSS (kUpdLossPpo, or kUpdLossA2c for k_a2c_grad<OD>,
+// b747_a2c_update.hip), the arguments of k_ppo_grad and pa (read with POP only).
 // POP: member p = blockIdx.y reads its own parameters and perm row and writes its own slice of the workspace --
 // workgroup-uniform offsets, applied once here; blockIdx.x and gridDim.x are what a launch of the member alone has.
     if constexpr (POP) {
@@ -43,14 +44,19 @@
         lds[L::hb + 1] = theta[P.bv];
         lds[L::ls] = theta[P.log_std];
     }
-    if (tid == 0) {   // the minibatch's advantage statistics from the blocks' partial sums, in block order
+    // the minibatch's advantage statistics from the blocks' partial sums, in block order (A2C with adv_part NULL -- no
+    // normalize_advantage, no statistics launch: mean 0 and factor 1, A = adv)
+    if (tid == 0 && LOSS == kUpdLossA2c && !adv_part) {
+        adv_ms[0] = 0.0;
+        adv_ms[1] = 1.0;
+    } else if (tid == 0) {
         double s = 0.0, q = 0.0;
         for (int b = 0; b < kUpdAdvBlocks; ++b) {
             s += adv_part[2 * b];
             q += adv_part[2 * b + 1];
         }
         const double n = (double)batch, var = (q - s * s / n) / (n - 1.0);
-        adv_ms[0] = (double)adv[idx[0]] + s / n;
+        adv_ms[0] = (double)adv[upd_row<LOSS>(idx, 0)] + s / n;
         adv_ms[1] = 1.0 / (sqrt(var > 0.0 ? var : 0.0) + 1e-8);
     }
     __syncthreads();
@@ -62,8 +68,8 @@
     acc.zero();
     double sums[kUpdSums] = {};
     const UpdRowArgs ra{obs, act, old_logp, adv, ret, idx, batch, clip, vf_coef, adv_ms[0], adv_ms[1]};
-    if (wave < 2) upd_tiles<OD, 0>(lds, wv, ra, lane, blockIdx.x * 2 + (wave & 1), gridDim.x * 2, acc, sums);
-    else upd_tiles<OD, 1>(lds, wv, ra, lane, blockIdx.x * 2 + (wave & 1), gridDim.x * 2, acc, sums);
+    if (wave < 2) upd_tiles<OD, 0, LOSS>(lds, wv, ra, lane, blockIdx.x * 2 + (wave & 1), gridDim.x * 2, acc, sums);
+    else upd_tiles<OD, 1, LOSS>(lds, wv, ra, lane, blockIdx.x * 2 + (wave & 1), gridDim.x * 2, acc, sums);
 
     // ---- the waves' accumulators into one vector (waves 0 and 2 store their net's part, then 1 and 3 add theirs)
     __syncthreads();                     // every wave is done with the fragments: their region becomes the vector

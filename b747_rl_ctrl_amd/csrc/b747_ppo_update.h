@@ -40,6 +40,11 @@ constexpr int kUpdTile = 32;        // rows per wave tile (the N of the 32x32 MF
 constexpr int kUpdStride = 33;      // row stride of the transposition scratch
 constexpr int kUpdAdamBlock = 1024;
 
+// The loss a gradient kernel computes per row (a template / in-scope constant of the shared pieces below; kUpdLossPpo
+// compiles to the code they had before there was a second one).  kUpdLossA2c: b747_a2c_update.h -- no ratio, no clip,
+// and `idx` may be NULL (the rows 0 .. batch - 1 in order).
+constexpr int kUpdLossPpo = 0, kUpdLossA2c = 1;
+
 // Workspace (bytes): [adv partials: double 2 x kUpdAdvBlocks][sum partials: double kUpdSums x kUpdMaxWG]
 // [gradient partials: float P x kUpdMaxWG]
 B747_HD constexpr int64_t upd_ws_adv() { return 0; }
@@ -203,11 +208,23 @@ __device__ __forceinline__ T upd_wave_sum(T x)
     return x;
 }
 
+// The rollout row at position j of the minibatch: idx[j]; for A2C, whose idx may be NULL, j itself then
+template <int LOSS>
+__device__ __forceinline__ int64_t upd_row(const int64_t *__restrict__ idx, int64_t j)
+{
+    if constexpr (LOSS == kUpdLossA2c) return idx ? idx[j] : j;
+    else return idx[j];
+}
+
+// B747_PPO_UPDATE_PIECES_ONLY: the device functions and the kernel bodies' helpers without the PPO kernels themselves,
+// for a translation unit that builds kernels of its own from them (b747_a2c_update.hip)
+#ifndef B747_PPO_UPDATE_PIECES_ONLY
 // Sum and sum of squares of adv[idx[j]] - adv[idx[0]] over the block's share of the minibatch, in fp64
 __global__ __launch_bounds__(256) void k_ppo_adv_stats(const float *__restrict__ adv, const int64_t *__restrict__ idx,
                                                        int64_t batch, double *__restrict__ part)
 {
     constexpr bool POP = false;
+    constexpr int LOSS = kUpdLossPpo;
     constexpr UpdPopArgs pa{0, 0, 0, 0, 0};   // (named by the discarded branch of the body only)
 #include "b747_ppo_adv_stats_body.h"
 }
@@ -217,8 +234,10 @@ __global__ __launch_bounds__(256) void k_pop_adv_stats(const float *__restrict__
                                                        int64_t batch, double *__restrict__ part, UpdPopArgs pa)
 {
     constexpr bool POP = true;
+    constexpr int LOSS = kUpdLossPpo;
 #include "b747_ppo_adv_stats_body.h"
 }
+#endif  // B747_PPO_UPDATE_PIECES_ONLY
 
 // Accumulators of one net, lane-partial: the dW2 tiles in the C/D layout ([mt][nt]: W2 row 32 mt + C/D row, column
 // 32 nt + (lane & 31)); the others for unit 32 mt + (lane & 31), summed over the rows of parity lane >> 5
@@ -422,8 +441,11 @@ struct UpdRowArgs {
     double clip, vf_coef, adv_mean, adv_inv;
 };
 
-// One net (0 policy, 1 value) over the tiles first, first + stride, ...: forward, the row's loss terms, backward
-template <int OD, int NET>
+// One net (0 policy, 1 value) over the tiles first, first + stride, ...: forward, the row's loss terms, backward.
+// LOSS selects the policy net's row math (the value net's is the same for both): kUpdLossPpo the clipped surrogate;
+// kUpdLossA2c -A logp with g_logp = -A / B on every row, the sums A logp in slot 0 and |A logp| in slot 4, slots 2, 3
+// and 5 left 0, old_logp and clip not read.
+template <int OD, int NET, int LOSS = kUpdLossPpo>
 __device__ __forceinline__ void upd_tiles(const float *__restrict__ lds, float *__restrict__ wv, const UpdRowArgs &a,
                                           int lane, int64_t first, int64_t stride, UpdNetAcc<OD> &acc,
                                           double (&sums)[kUpdSums])
@@ -437,7 +459,7 @@ __device__ __forceinline__ void upd_tiles(const float *__restrict__ lds, float *
     for (int64_t tile = first; tile < tiles; tile += stride) {
         const int64_t j = tile * kUpdTile + rl;
         const bool valid = j < a.batch, count = valid && h == 0;
-        const int64_t row = a.idx[valid ? j : a.batch - 1];
+        const int64_t row = upd_row<LOSS>(a.idx, valid ? j : a.batch - 1);
         float o[OD];
 #pragma unroll
         for (int k = 0; k < OD; ++k) o[k] = a.obs[row * OD + k];
@@ -449,7 +471,20 @@ __device__ __forceinline__ void upd_tiles(const float *__restrict__ lds, float *
         // that the sums that cancel -- the head biases' and log_std's gradients -- carry the forward's error only
         float h1[32], h2[32];
         double out, g;
-        if constexpr (NET == 0) {
+        if constexpr (NET == 0 && LOSS == kUpdLossA2c) {
+            const double a_row = (double)a.act[row];
+            const double an = ((double)a.adv[row] - a.adv_mean) * a.adv_inv;   // (mean 0, factor 1: adv itself, exactly)
+            upd_forward<OD, 0>(lds, wv, o, lane, h1, h2, out);
+            const double diff = a_row - out, q = diff * diff * inv_var;
+            const double logp = (-0.5 * q - (double)log_std) - 0.918938533204672742;
+            const double g_logp = valid ? -(an * inv_b) : 0.0;
+            if (count) {
+                sums[0] += an * logp;
+                sums[4] += fabs(an * logp);
+                sums[8] += g_logp * (q - 1.0);
+            }
+            g = g_logp * (diff * inv_var);
+        } else if constexpr (NET == 0) {
             const double a_row = (double)a.act[row], olp = (double)a.old_logp[row];
             const double an = ((double)a.adv[row] - a.adv_mean) * a.adv_inv;
             upd_forward<OD, 0>(lds, wv, o, lane, h1, h2, out);
@@ -480,6 +515,7 @@ __device__ __forceinline__ void upd_tiles(const float *__restrict__ lds, float *
     }
 }
 
+#ifndef B747_PPO_UPDATE_PIECES_ONLY
 // See the head of the file.  sums (per workgroup, fp64): min(A ratio, A clamp(ratio)), (ret - value)^2, [|ratio - 1|
 // > clip], (ratio - 1) - log ratio, |A ratio|, |ratio| + 1 + |log ratio| over the workgroup's rows, then dLoss/d mean,
 // dLoss/d value and dLoss/d log_std summed over them.
@@ -493,6 +529,7 @@ __global__ __launch_bounds__(256) void k_ppo_grad(const float *__restrict__ thet
                                                   double *__restrict__ spart)
 {
     constexpr bool POP = false;
+    constexpr int LOSS = kUpdLossPpo;
     constexpr UpdPopArgs pa{0, 0, 0, 0, 0};   // (named by the discarded branch of the body only)
 #include "b747_ppo_grad_body.h"
 }
@@ -509,6 +546,7 @@ __global__ __launch_bounds__(256) void k_pop_grad(const float *__restrict__ thet
                                                   double *__restrict__ spart, UpdPopArgs pa)
 {
     constexpr bool POP = true;
+    constexpr int LOSS = kUpdLossPpo;
 #include "b747_ppo_grad_body.h"
 }
 
@@ -581,6 +619,7 @@ __global__ __launch_bounds__(256) void k_hyp_grad(const float *__restrict__ thet
     constexpr bool POP = true;
     const double *hyp = hyper_dev + (int64_t)blockIdx.y * B747_PPO_HYPER_COLS;
     const double clip = hyp[B747_PPO_HYPER_CLIP_RANGE], vf_coef = hyp[B747_PPO_HYPER_VF_COEF];
+    constexpr int LOSS = kUpdLossPpo;
 #include "b747_ppo_grad_body.h"
 }
 
@@ -610,6 +649,8 @@ __global__ __launch_bounds__(kUpdAdamBlock) void k_hyp_adam(float *__restrict__ 
     const double max_norm = hyp[B747_PPO_HYPER_MAX_GRAD_NORM], lr = hyp[B747_PPO_HYPER_LR];
 #include "b747_ppo_adam_body.h"
 }
+
+#endif  // B747_PPO_UPDATE_PIECES_ONLY
 
 #endif  // B747_PPO_UPDATE_NO_KERNELS
 

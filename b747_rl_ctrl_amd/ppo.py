@@ -655,6 +655,229 @@ class PPO:
         return run_step_tests_fused(policy, vartheta_ref, state0=state0, tk=e.tk if tk is None else tk, **kw)
 
 
+@dataclass
+class A2CConfig:
+    """SB3 1.4 A2C's defaults.  optimizer: "rmsprop" (torch.optim.RMSprop(alpha=rms_alpha, eps=rms_eps): SB3's
+    use_rms_prop=True), "rmsprop_tf" (SB3's RMSpropTFLike, below) or "adam" (torch.optim.Adam(eps=1e-5), betas 0.9 /
+    0.999: SB3's use_rms_prop=False; rms_alpha and rms_eps are not read)."""
+    n_steps: int = 5
+    gamma: float = 0.99
+    gae_lambda: float = 1.0
+    ent_coef: float = 0.0
+    vf_coef: float = 0.5
+    max_grad_norm: float = 0.5
+    learning_rate: float = 7e-4
+    normalize_advantage: bool = False
+    optimizer: str = "rmsprop"
+    rms_alpha: float = 0.99
+    rms_eps: float = 1e-5
+
+    @classmethod
+    def reference(cls, **kw) -> "A2CConfig":
+        """The reference's own entry, neural/setups.py hyperparams[A2C]: optimizer_class=RMSpropTFLike with
+        optimizer_kwargs=dict(eps=1e-9) on the 64-64 tanh nets, everything else SB3's default"""
+        return cls(**({"optimizer": "rmsprop_tf", "rms_eps": 1e-9} | kw))
+
+
+A2C_OPTIMIZERS = ("adam", "rmsprop", "rmsprop_tf")      # by B747_OPT_* value (include/b747.h)
+
+
+class RMSpropTFLike(torch.optim.Optimizer):
+    """SB3's RMSpropTFLike (stable_baselines3/common/sb2_compat/rmsprop_tf_like.py) without momentum, centring or
+    weight decay: sq = alpha sq + (1 - alpha) g^2, theta -= lr g / sqrt(sq + eps) -- epsilon inside the square root --
+    with sq starting at ONES (TensorFlow's initial accumulator)."""
+
+    def __init__(self, params, lr: float = 7e-4, alpha: float = 0.99, eps: float = 1e-5):
+        super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps))
+
+    @torch.no_grad()
+    def step(self):
+        for group in self.param_groups:
+            for prm in group["params"]:
+                if prm.grad is None:
+                    continue
+                st = self.state[prm]
+                if not st:
+                    st["step"], st["square_avg"] = 0, torch.ones_like(prm)
+                st["step"] += 1
+                sq = st["square_avg"]
+                sq.mul_(group["alpha"]).addcmul_(prm.grad, prm.grad, value=1 - group["alpha"])
+                prm.addcdiv_(prm.grad, sq.add(group["eps"]).sqrt_(), value=-group["lr"])
+
+
+class A2C(PPO):
+    """Device-resident A2C on a BatchControllerEnv (SB3 1.4 A2C): PPO's policy, buffers, rollout kernels,
+    GAE, step tests and data-parallel set-up, with ONE gradient step per rollout over all its n_steps * n rows.
+
+    fused_update=False (default; the reference math): torch autograd, clip_grad_norm_ and self.opt, the optimiser
+    cfg.optimizer names.  fused_update=True: one b747_a2c_update call on self.flat (include/b747.h) -- the loss and
+    gradient kernel, then k_ppo_rmsprop or k_ppo_adam; the optimiser state is upd_sq (ones for "rmsprop_tf") or upd_m /
+    upd_v, with the step count upd_t, and self.opt is left alone.  Data-parallel training keeps two calls (b747_a2c_grad,
+    then the optimiser's with grad_scale 1 / world), the all-reduce of the flat gradient between them.  Either path
+    leaves its statistics row in upd_stats [8] (b747_a2c_grad's layout)."""
+
+    def __init__(self, env: BatchControllerEnv, cfg: Optional[A2CConfig] = None, seed: int = 0, fused: bool = True,
+                 rollout_kernel: Union[bool, str, None] = None, process_group=None, data_parallel: Optional[bool] = None,
+                 fused_update: bool = False, gae_kernel: Optional[bool] = None):
+        cfg = cfg or A2CConfig()
+        if cfg.optimizer not in A2C_OPTIMIZERS:
+            raise ValueError(f"A2CConfig.optimizer={cfg.optimizer!r}: \"rmsprop\", \"rmsprop_tf\" or \"adam\"")
+        super().__init__(env, cfg, seed=seed, fused=fused, rollout_kernel=rollout_kernel, process_group=process_group,
+                         data_parallel=data_parallel, fused_update=fused_update, gae_kernel=gae_kernel)
+        self.epoch_call = False                   # (PPO's minibatch loop: not A2C's)
+        prm, lr = self.policy.parameters(), cfg.learning_rate
+        if cfg.optimizer == "rmsprop":
+            self.opt = torch.optim.RMSprop(prm, lr=lr, alpha=cfg.rms_alpha, eps=cfg.rms_eps)
+        elif cfg.optimizer == "rmsprop_tf":
+            self.opt = RMSpropTFLike(prm, lr=lr, alpha=cfg.rms_alpha, eps=cfg.rms_eps)
+        else:
+            self.opt = torch.optim.Adam(prm, lr=lr, eps=1e-5)
+        self.upd_stats = torch.zeros(8, dtype=torch.float32, device=env.device)
+        self._it_graph, self._it_graph_key = None, None
+        if self.fused_update and cfg.optimizer != "adam":     # RMSprop's one state vector in place of Adam's two
+            del self.upd_m, self.upd_v
+            self.upd_sq = torch.full((self.n_params,), 1.0 if cfg.optimizer == "rmsprop_tf" else 0.0,
+                                     dtype=torch.float32, device=env.device)
+
+    # ---------------------------------------------------------------- update --
+    def _update_torch(self, N: int, T: int):
+        """SB3 A2C.train on the first N rows of the rollout: one step of self.opt; the statistics into upd_stats"""
+        c = self.cfg
+        obs, act = self.obs_buf[:T].reshape(N, -1), self.act_buf[:T].reshape(N, -1)
+        adv, ret = self.adv_buf[:T].reshape(N), self.ret_buf[:T].reshape(N)
+        mean, value = self.policy(obs)
+        logp = self.policy.log_prob(mean, act)
+        a = (adv - adv.mean()) / (adv.std() + 1e-8) if c.normalize_advantage else adv
+        pl = -(a * logp).mean()
+        vf = ((ret - value) ** 2).mean()
+        ent_loss = -self.policy.entropy()
+        loss = pl + c.ent_coef * ent_loss + c.vf_coef * vf
+        with torch.no_grad():
+            zero = torch.zeros_like(pl)
+            self.upd_stats.copy_(torch.stack([pl, vf, ent_loss, zero, zero, (a * logp).abs().mean(), zero, loss]))
+        self.opt.zero_grad(set_to_none=True)
+        loss.backward()
+        if self.data_parallel:
+            allreduce_gradients(self.policy.parameters(), self.group)
+        nn.utils.clip_grad_norm_(self.policy.parameters(), c.max_grad_norm)
+        self.opt.step()
+
+    def _update_fused(self, N: int):
+        """_update_torch as stream-ordered calls on self.flat[:n_params] (no host synchronisation): one
+        b747_a2c_update; data-parallel, b747_a2c_grad, the all-reduce of the flat gradient and the optimiser's call with
+        its 1 / world.  idx is NULL: the first N rows of the time-major buffers, in order."""
+        c, p, L = self.cfg, _p, self._L
+        stream = torch.cuda.current_stream().cuda_stream
+        opt = A2C_OPTIMIZERS.index(c.optimizer)
+        adam = c.optimizer == "adam"
+        rows = (p(self.flat), self.env.obs_dim, p(self.obs_buf), p(self.act_buf), p(self.adv_buf), p(self.ret_buf), None,
+                N, int(c.normalize_advantage), c.ent_coef, c.vf_coef, p(self.upd_ws), p(self.upd_grad), p(self.upd_stats))
+        if not (self.data_parallel and dist.is_available() and dist.is_initialized()):
+            self._lib.check(L.b747_a2c_update(
+                *rows, opt, p(self.upd_m if adam else self.upd_sq), p(self.upd_v) if adam else None, p(self.upd_t),
+                c.max_grad_norm, c.learning_rate, c.rms_alpha, 1e-5 if adam else c.rms_eps, stream), "b747_a2c_update")
+            return
+        self._lib.check(L.b747_a2c_grad(*rows, stream), "b747_a2c_grad")
+        world = _world(self.group)
+        dist.all_reduce(self.upd_grad, op=dist.ReduceOp.SUM, group=self.group)
+        if adam:
+            self._lib.check(L.b747_ppo_adam(
+                p(self.flat), p(self.upd_m), p(self.upd_v), p(self.upd_t), p(self.upd_grad), self.n_params, 1.0 / world,
+                c.max_grad_norm, c.learning_rate, 0.9, 0.999, 1e-5, stream), "b747_ppo_adam")
+        else:
+            self._lib.check(L.b747_ppo_rmsprop(
+                p(self.flat), p(self.upd_sq), p(self.upd_t), p(self.upd_grad), self.n_params, 1.0 / world,
+                c.max_grad_norm, c.learning_rate, c.rms_alpha, c.rms_eps, int(c.optimizer == "rmsprop_tf"), stream),
+                "b747_ppo_rmsprop")
+
+    def _update(self, T: int):
+        """train()'s device work: the step, then the modules and the packed buffer brought up to date -- stream-ordered,
+        and with fused_update free of host reads and synchronisation (learn(use_graph=True) captures it)"""
+        N = T * self.env.n
+        if self.fused_update:
+            self._update_fused(N)
+            load_flat(self.policy, self.flat)     # the flat vector is the master copy: hand it to the modules,
+            self._lib.check(self._L.b747_policy_pack(   # and derive the packed sections the rollout kernels read
+                self.flat.data_ptr(), self.env.obs_dim, torch.cuda.current_stream().cuda_stream), "b747_policy_pack")
+        else:
+            self._update_torch(N, T)
+            self.sync_params()
+
+    @torch.no_grad()
+    def _train_stats(self, T: int) -> dict:
+        """train()'s return value from upd_stats and the rollout buffers (one host synchronisation)"""
+        N = T * self.env.n
+        v, r = self.val_buf[:T].reshape(N), self.ret_buf[:T].reshape(N)
+        var_r = r.var(unbiased=False)
+        ev = 1 - (r - v).var(unbiased=False) / var_r if float(var_r) != 0 else torch.tensor(float("nan"))
+        st = self.upd_stats.tolist()
+        return {"policy_loss": st[0], "value_loss": st[1], "entropy_loss": st[2], "loss": st[7],
+                "explained_variance": float(ev), "std": float(self.policy.log_std.exp().mean()), "pg_term_scale": st[5]}
+
+    def train(self, T: Optional[int] = None):
+        """One gradient step over all T * n rows of the rollout (SB3 1.4 A2C.train).  Returns SB3's train/* log values
+        for A2C -- policy_loss, value_loss, entropy_loss, explained_variance (of the rollout's values against its
+        returns), std and loss -- and, not an SB3 value, pg_term_scale = mean |A logp|, the magnitude of the terms the
+        cancelling policy-loss mean sums (its float32 rounding scale)."""
+        T = T or self.cfg.n_steps
+        self._update(T)
+        return self._train_stats(T)
+
+    # ----------------------------------------------------------------- learn --
+    def _iteration(self, T: int):
+        """One iteration's device work: rollout, bootstrap value and GAE, update, repack"""
+        self.collect_rollouts(T, use_graph=False)
+        self.compute_gae(T)
+        self._update(T)
+
+    def _replay_iteration(self, T: int):
+        """_iteration as one replay of a HIP graph captured on one stream (a linear graph: every call is stream-ordered
+        behind the one before), captured when there is none for this key (PPO._graph_key; the capture launches nothing:
+        the first iteration is a replay too).  The kernels read step_base, the parameters and the optimiser state on the
+        device when they run."""
+        key = self._graph_key(T)
+        if self._it_graph is None or self._it_graph_key != key:
+            s = torch.cuda.Stream(device=self.env.device)
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s), torch.no_grad():     # warm up the bootstrap forward's kernels (no state changes)
+                self.policy(self.last_obs)
+            torch.cuda.current_stream().wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=s), torch.no_grad():
+                self._iteration(T)
+            self._it_graph, self._it_graph_key = g, key
+        self._it_graph.replay()
+
+    def learn(self, iterations: int, n_steps: Optional[int] = None, control_test=None, use_graph: bool = False):
+        """PPO.learn for A2C: `iterations` x (collect_rollouts, compute_gae, train) after an env reset; train()'s values
+        per iteration, with mean_reward; control_test as PPO.learn's.  use_graph=True (needs fused_update=True and a
+        rollout kernel: nothing of the iteration may run on the host) replays each iteration's device work as one HIP
+        graph (_replay_iteration) and reads the statistics outside it; the same bits as use_graph=False.  The step
+        tests stay outside the capture, before the iteration's replay.  With five-step rollouts an iteration is a
+        handful of launches: this is the form A2C is meant to run in."""
+        T = n_steps or self.cfg.n_steps
+        assert T <= self.cfg.n_steps
+        control_test = self.control_test if control_test is None else control_test
+        pushes = _control_test_plan(self, control_test, iterations, T)
+        if use_graph and not (self.fused_update and self.rollout_kernel):
+            raise ValueError("A2C.learn(use_graph=True) needs fused_update=True and a rollout kernel (the torch update "
+                             "and the two-launch rollout do host work that a capture would freeze)")
+        self.last_obs.copy_(self.env.reset())
+        self._last_obs_from_env = False
+        hist = []
+        for it in range(iterations):
+            if pushes is not None and pushes[it]:
+                control_test.evaluate(pushes[it])
+            if use_graph:
+                self._replay_iteration(T)
+            else:
+                self._iteration(T)
+            hist.append(self._train_stats(T) | {"mean_reward": float(self.rew_buf[:T].mean())})
+            if pushes is not None:
+                hist[-1].update(control_test.history_entry())
+        return hist
+
+
 class PopulationPPO:
     """P independent PPO learners on ONE BatchControllerEnv, their rollouts flown side by side in one launch
     (b747_ppo_rollout_population, include/b747.h).

@@ -41,7 +41,8 @@ extern "C" {
                                 * b747_policy_pack_batch.  b747_ppo_rollout_population, b747_ppo_epoch_population,
                                 * b747_ppo_epoch_batched_workspace and b747_ppo_epoch_batched, then
                                 * b747_ppo_gae_population, b747_ppo_epoch_population_hyper and b747_ppo_epoch_batched_hyper,
-                                * then b747_ppo_sample_orders, then b747_ppo_track_best
+                                * then b747_ppo_sample_orders, then b747_ppo_track_best, then b747_a2c_grad,
+                                * b747_ppo_rmsprop and b747_a2c_update
                                 * came later as purely additive entry points under 15 (no struct, argument or
                                 * behaviour of an existing one changed): a library built before them still reports
                                 * 15, and a binding catches it by the missing entry point (_lib.bind) */
@@ -659,6 +660,47 @@ int32_t b747_ppo_track_best(const double *eval_out /* device, [B747_NEVAL][n_eva
                             double *ring /* device, [3][n_members][window] */, int64_t *count, double *last,
                             double *window_mean, double *best_quality, int64_t *best_eval,
                             float *best_params /* device, [n_members][stride] */, void *stream);
+
+/* ---- one A2C update on the device (additive under ABI 15; ppo.A2C; SB3 1.4 A2C.train) ----
+ * For the policy of b747_ppo_grad (the same theta, the same obs_dims) ONE gradient step over the rows r = idx[0 .. batch)
+ * of the time-major rollout buffers -- idx may be NULL: the rows 0 .. batch - 1, A2C's whole buffer -- of the loss
+ *   mean(-A logp) + ent_coef (-entropy) + vf_coef mean((ret - value)^2)
+ * with A = adv, or with normalize_advantage != 0 A = (adv - mean) / (std + 1e-8) over the batch (unbiased std, fp64 sums:
+ * b747_ppo_grad's statistics; without it that launch is skipped).  Two calls, so that a data-parallel all-reduce of the
+ * flat gradient fits between them, or b747_a2c_update for both; all stream-ordered and graph-capturable, no allocation,
+ * no synchronisation, no floating-point atomics: the same inputs give the same bits.  All pointers are device memory.
+ *
+ * b747_a2c_grad: grad [P] = the loss's gradient (flat_params order); stats [8] = the policy loss mean(-A logp), the
+ * value loss, the entropy loss, 0, 0, mean |A logp| (the magnitude of the terms the policy loss sums), 0, and the loss.
+ * b747_ppo_grad's arithmetic (fp64 forward, fp32 matrix-core backward products, the gradients of action_net.bias,
+ * value_net.bias and log_std summed in fp64), grid and workspace (b747_ppo_update_workspace(obs_dim) bytes).  batch >= 1;
+ * >= 2 with normalize_advantage.
+ * b747_ppo_rmsprop: g = grad_scale grad; coef = min(1, max_grad_norm / (|g|_2 + 1e-6)) (torch clip_grad_norm_); gc = g
+ * coef; sq = alpha sq + (1 - alpha) gc^2; theta -= lr gc / (sqrt(sq) + eps) (tf_like == 0: torch.optim.RMSprop, not
+ * centred, momentum 0, no weight decay; sq starts at zeros) or theta -= lr gc / sqrt(sq + eps) (tf_like != 0: SB3's
+ * RMSpropTFLike; sq starts at ONES, which the caller fills); *t += 1 (one device int64, as b747_ppo_adam's).  theta, sq
+ * [n_params]; element arithmetic in fp64, stored as fp32; grad is not modified.
+ * b747_a2c_update: the launches of b747_a2c_grad, then those of the optimiser with grad_scale 1 and n_params = P, from
+ * one host call -- the same kernels, arguments and order, the same bits.  optimizer B747_OPT_RMSPROP / _RMSPROP_TF:
+ * b747_ppo_rmsprop on state0 = sq (state1 is not read and may be NULL) with alpha and eps.  B747_OPT_ADAM: b747_ppo_adam
+ * on state0 = m, state1 = v with betas 0.9 / 0.999 and eps (SB3's use_rms_prop=False; alpha is not read).
+ * All return -hipErrorInvalidValue, before anything reaches the device (b747_last_error names the argument), for a
+ * NULL pointer other than idx (and state1 where it is not read), an obs_dim without kernels, batch < 1 (< 2 with
+ * normalize_advantage), n_params < 1, an lr, eps or max_grad_norm that is not finite and above 0, alpha outside [0, 1)
+ * or an unknown optimizer. */
+#define B747_OPT_ADAM 0
+#define B747_OPT_RMSPROP 1
+#define B747_OPT_RMSPROP_TF 2
+int32_t b747_a2c_grad(const float *theta, int32_t obs_dim, const float *obs, const float *act, const float *adv,
+                      const float *ret, const int64_t *idx /* may be NULL */, int64_t batch, int32_t normalize_advantage,
+                      double ent_coef, double vf_coef, void *workspace, float *grad, float *stats, void *stream);
+int32_t b747_ppo_rmsprop(float *theta, float *sq, int64_t *t, const float *grad, int64_t n_params, double grad_scale,
+                         double max_grad_norm, double lr, double alpha, double eps, int32_t tf_like, void *stream);
+int32_t b747_a2c_update(float *theta, int32_t obs_dim, const float *obs, const float *act, const float *adv,
+                        const float *ret, const int64_t *idx /* may be NULL */, int64_t batch,
+                        int32_t normalize_advantage, double ent_coef, double vf_coef, void *workspace, float *grad,
+                        float *stats, int32_t optimizer, float *state0, float *state1 /* Adam's v, else may be NULL */,
+                        int64_t *t, double max_grad_norm, double lr, double alpha, double eps, void *stream);
 
 /* Human-readable text of the last error returned on this thread. */
 const char *b747_last_error(void);
