@@ -122,6 +122,11 @@ SIGNATURES = {
     "b747_ppo_rmsprop": ([_V, _V, _V, _V, _I64] + [_F64] * 5 + [_I32, _V], _I32),
     "b747_a2c_update": ([_V, _I32] + [_V] * 5 + [_I64, _I32, _F64, _F64, _V, _V, _V, _I32, _V, _V, _V] + [_F64] * 4 + [_V],
                         _I32),
+    # (A2C for a population: theta, n_policies, policy_stride, obs_dim, obs, act, adv, ret, rows, rows_stride, batch,
+    #  normalize_advantage, hyper_dev, workspace, workspace_bytes, state0, state1, t, rms_alpha, rms_eps, adam_beta1,
+    #  adam_beta2, adam_eps, stats)
+    "b747_a2c_update_population": ([_V, _I32, _I64, _I32] + [_V] * 5 + [_I64, _I64, _I32, _V, _V, _I64, _V, _V, _V]
+                                   + [_F64] * 5 + [_V, _V], _I32),
 }
 
 

@@ -29,6 +29,7 @@
 #define B747_PPO_UPDATE_NO_KERNELS   // the update kernels live in b747_ppo_update.hip; this unit calls their launchers
 #include "b747_ppo_update.h"
 #include "b747_a2c_update.h"
+#include "b747_a2c_population.h"
 #include "b747_ppo_gae.h"
 #include "b747_ppo_order.h"
 #include "b747_ppo_track.h"
@@ -514,6 +515,42 @@ B747_API int32_t b747_a2c_update(float *theta, int32_t obs_dim, const float *obs
                                            {max_grad_norm, 0.9, 0.999, eps}, lr, s));
     return launched(W, launch_ppo_rmsprop(theta, state0, t, grad, n_params, 1.0,
                                           {max_grad_norm, alpha, eps, optimizer == B747_OPT_RMSPROP_TF}, lr, s));
+}
+
+B747_API int32_t b747_a2c_update_population(float *theta, int32_t n_policies, int64_t policy_stride, int32_t obs_dim,
+                                            const float *obs, const float *act, const float *adv, const float *ret,
+                                            const int64_t *rows, int64_t rows_stride, int64_t batch,
+                                            int32_t normalize_advantage, const double *hyper_dev, void *workspace,
+                                            int64_t workspace_bytes, float *state0, float *state1, int64_t *t,
+                                            double rms_alpha, double rms_eps, double adam_beta1, double adam_beta2,
+                                            double adam_eps, float *stats, void *stream)
+{
+    const char *const W = "b747_a2c_update_population";
+    const UpdData d{obs, act, nullptr, adv, ret};
+    if (int32_t e = check_upd_policy(W, theta, obs_dim)) return e;
+    if (int32_t e = check_upd_members(W, n_policies, policy_stride, obs_dim)) return e;
+    if (int32_t e = check_not_null(W, {{obs, "obs"}, {act, "act"}, {adv, "adv"}, {ret, "ret"}, {rows, "rows"}})) return e;
+    if (batch < 1) return bad_arg(W, "batch < 1");
+    if (normalize_advantage && batch < 2)
+        return bad_arg(W, "batch < 2 with normalize_advantage (the advantages' standard deviation needs two rows)");
+    if (rows_stride < batch) return bad_arg(W, "rows_stride < batch (a member's row of the index table holds its batch)");
+    if (!hyper_dev)
+        return bad_arg(W, "hyper_dev is NULL (a device table, one row of B747_PPO_HYPER_COLS doubles per member)");
+    if (int32_t e = check_not_null(W, {{workspace, "workspace"}})) return e;
+    if (workspace_bytes < upd_pop_ws_bytes(obs_dim, batch))
+        return bad_arg(W, "workspace_bytes (below one member's b747_ppo_epoch_batched_workspace(obs_dim, batch))");
+    if (int32_t e = check_not_null(W, {{state0, "state0"}, {state1, "state1"}, {t, "t"}})) return e;
+    if (!(rms_alpha >= 0.0 && rms_alpha < 1.0)) return bad_arg(W, "rms_alpha (outside [0, 1))");
+    if (!(isfinite(rms_eps) && rms_eps > 0.0)) return bad_arg(W, "rms_eps (not finite and above 0)");
+    if (!(adam_beta1 >= 0.0 && adam_beta1 < 1.0)) return bad_arg(W, "adam_beta1 (outside [0, 1))");
+    if (!(adam_beta2 >= 0.0 && adam_beta2 < 1.0)) return bad_arg(W, "adam_beta2 (outside [0, 1))");
+    if (!(isfinite(adam_eps) && adam_eps > 0.0)) return bad_arg(W, "adam_eps (not finite and above 0)");
+    if (!stats) return bad_arg(W, "stats is NULL");
+    return launched(W, launch_a2c_update_population({theta, state0, state1, t}, n_policies, policy_stride, obs_dim, d,
+                                                    rows, rows_stride, batch, normalize_advantage != 0, hyper_dev,
+                                                    workspace, workspace_bytes,
+                                                    {rms_alpha, rms_eps, adam_beta1, adam_beta2, adam_eps}, stats,
+                                                    (hipStream_t)stream));
 }
 
 B747_API int32_t b747_ppo_gae(const float *rew, const float *val, const uint8_t *done, const float *last_value,

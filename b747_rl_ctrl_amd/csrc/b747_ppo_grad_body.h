@@ -1,14 +1,16 @@
 // b747_ppo_grad_body.h -- the body of k_ppo_grad<OD> and of its member-batched sibling k_pop_grad<OD>
 // (b747_ppo_update.h).  Textual, not an inlined function, as b747_eval_body.h: the existing kernels keep their
 // instruction streams.  In scope where it is included: OD, POP, LOSS (kUpdLossPpo, or kUpdLossA2c for k_a2c_grad<OD>,
-// b747_a2c_update.hip), the arguments of k_ppo_grad and pa (read with POP only).
+// b747_a2c_update.hip, and k_apop_grad<OD>, b747_a2c_population.hip), the arguments of k_ppo_grad and pa (read with POP
+// only).
 // POP: member p = blockIdx.y reads its own parameters and perm row and writes its own slice of the workspace --
 // workgroup-uniform offsets, applied once here; blockIdx.x and gridDim.x are what a launch of the member alone has.
     if constexpr (POP) {
         const int64_t ws_off = (int64_t)blockIdx.y * pa.ws_stride;
         theta += (int64_t)blockIdx.y * pa.policy_stride;
         idx += (int64_t)blockIdx.y * pa.n_rows;
-        adv_part = reinterpret_cast<const double *>(reinterpret_cast<const char *>(adv_part) + ws_off);
+        if (LOSS != kUpdLossA2c || adv_part)   // (A2C's NULL -- no normalize_advantage -- stays NULL for every member)
+            adv_part = reinterpret_cast<const double *>(reinterpret_cast<const char *>(adv_part) + ws_off);
         gpart = reinterpret_cast<float *>(reinterpret_cast<char *>(gpart) + ws_off);
         spart = reinterpret_cast<double *>(reinterpret_cast<char *>(spart) + ws_off);
     }

@@ -1263,6 +1263,252 @@ class PopulationPPO:
         return population_step_tests(self.flat, vartheta_ref, state0=state0, tk=e.tk if tk is None else tk, **kw)
 
 
+# The hyper-parameter table of a population of A2C learners: PPO's layout (HYPER_COLS, HYPER_COLUMN)
+# without clip_range -- column 1 is 0 -- and with the member's optimiser, its B747_OPT_* value, in column 7
+# (include/b747.h B747_PPO_HYPER_OPTIMIZER).  The keys are A2CConfig's names.
+A2C_HYPER_COLUMN = {"learning_rate": 0, "ent_coef": 2, "vf_coef": 3, "max_grad_norm": 4, "gamma": 5, "gae_lambda": 6,
+                    "optimizer": 7}
+
+
+def _check_a2c_hyper_value(key: str, x, where: str) -> float:
+    """x as the table's float if it is a value `key` may take: an A2C_OPTIMIZERS name for "optimizer" (stored as its
+    index, the B747_OPT_* value), _check_hyper_value's ranges for the others"""
+    if key != "optimizer":
+        return _check_hyper_value(key, x, where)
+    if x not in A2C_OPTIMIZERS:
+        raise ValueError(f"{where}: optimizer = {x!r}: one of {list(A2C_OPTIMIZERS)}")
+    return float(A2C_OPTIMIZERS.index(x))
+
+
+def a2c_hyper_table(cfg: A2CConfig, n_members: int, hyper=None, learning_rates=None) -> torch.Tensor:
+    """hyper_table for A2C learners: the [n_members, 8] float64 CPU table with columns A2C_HYPER_COLUMN (column 1, PPO's
+    clip_range, is 0).  hyper: None (every row is cfg's) or one dict per member with keys among learning_rate,
+    ent_coef, vf_coef, max_grad_norm, gamma, gae_lambda and optimizer (an A2C_OPTIMIZERS name); a key a member does not
+    name comes from cfg -- the learning rate from learning_rates[p] where that list is given (then no dict may name
+    learning_rate: one source per value).  ValueError for an unknown key (clip_range is one: A2C has none), a list of the
+    wrong length, an unknown optimizer or a value outside its range.  n_steps, normalize_advantage, rms_alpha, rms_eps
+    and the network are not keys: they stay the population's."""
+    P = int(n_members)
+    if P < 1:
+        raise ValueError(f"a2c_hyper_table: {P} members")
+    rows = [{}] * P if hyper is None else list(hyper)
+    if len(rows) != P or (learning_rates is not None and len(learning_rates) != P):
+        raise ValueError("a2c_hyper_table: hyper and learning_rates take one entry per member")
+    table = torch.zeros(P, HYPER_COLS, dtype=torch.float64)
+    for p, row in enumerate(rows):
+        unknown = sorted(set(row) - set(A2C_HYPER_COLUMN))
+        if unknown:
+            raise ValueError(f"a2c_hyper_table: member {p}: unknown key(s) {unknown}; a member's own values are "
+                             f"{sorted(A2C_HYPER_COLUMN)} (n_steps, normalize_advantage, RMSprop's alpha and eps and "
+                             f"the network are shared; A2C has no clip_range)")
+        if learning_rates is not None and "learning_rate" in row:
+            raise ValueError(f"a2c_hyper_table: member {p} names learning_rate although learning_rates is given")
+        for key, col in A2C_HYPER_COLUMN.items():
+            if key in row:
+                x = row[key]
+            elif key == "learning_rate" and learning_rates is not None:
+                x = learning_rates[p]
+            else:
+                x = getattr(cfg, key)
+            table[p, col] = _check_a2c_hyper_value(key, x, f"a2c_hyper_table: member {p}")
+    return table
+
+
+class PopulationA2C(PopulationPPO):
+    """P independent A2C learners on ONE BatchControllerEnv: PopulationPPO's members -- their envs,
+    policies from `seeds`, reward constants from `rew_configs`, the one-launch rollout with its bootstrap values
+    (b747_ppo_rollout_population), step_tests, member, repack -- with A2C's update: ONE gradient step per rollout over a
+    member's n_steps * envs_per_member rows, for all members from one b747_a2c_update_population call (include/b747.h;
+    the member on blockIdx.y of member-batched siblings of b747_a2c_update's kernels).  This is the shape of the
+    reference's ControllerAgent.optimize() with its default net_class=A2C: trials that differ in reward_config and in
+    gamma, gae_lambda, max_grad_norm, learning_rate, ent_coef, vf_coef and the optimiser (neural/setups.py,
+    trial_hyperparams), ranked by a ControlTest (`pop.control_test = ControlTest(pop, ...)`, as for PopulationPPO).
+
+    The population always has a hyper-parameter table (a2c_hyper_table: `hyper` [P, 8] on the CPU, `hyper_dev` on the
+    env's device; hyper=None makes every row cfg's): the GAE is one b747_ppo_gae_population launch and the update reads
+    each member's ent_coef, vf_coef, max_grad_norm, learning rate and optimiser from its row on the device.  Shared:
+    n_steps, normalize_advantage, rms_alpha, rms_eps and the network; Adam is eps 1e-5 with betas 0.9 / 0.999, as in
+    A2C.  The optimiser state is upd_s0 and upd_s1 [P, n_params] (RMSprop's square average -- ONES at first for an
+    "rmsprop_tf" member -- or Adam's m in upd_s0, Adam's v in upd_s1) with the step counts upd_t [P]; `stats` [P, 8] is
+    the persistent statistics buffer (b747_a2c_grad's row per member); `rows` [P, n_steps * envs_per_member] is the
+    members' index table (member_rows), built once.  Per member the bits are those of a separate learner composed from
+    the single-learner calls with the member's values (tests/test_gpu_a2c_population_train.py).
+
+    train() draws no sample order (A2C takes the whole rollout, in order): there is no minibatch_order or sample_order
+    here, and passing one is a ValueError.  learn(use_graph=True) replays rollout, GAE, update and repack as one HIP
+    graph per iteration."""
+
+    def __init__(self, env: BatchControllerEnv, n_members: int, envs_per_member: int = 64,
+                 cfg: Optional[A2CConfig] = None, seeds=None, rew_configs=None, learning_rates=None, seed: int = 0,
+                 hyper=None, **unsupported):
+        self._refuse("PopulationA2C", unsupported)
+        cfg = cfg or A2CConfig()
+        if cfg.optimizer not in A2C_OPTIMIZERS:
+            raise ValueError(f"A2CConfig.optimizer={cfg.optimizer!r}: \"rmsprop\", \"rmsprop_tf\" or \"adam\"")
+        P = int(n_members)
+        # (the table first, so that a refused value raises before any launch; a bad member count is the parent's to name)
+        table = a2c_hyper_table(cfg, P, hyper, learning_rates) if P >= 1 else None
+        super().__init__(env, P, envs_per_member, cfg, seeds=seeds, rew_configs=rew_configs,
+                         learning_rates=learning_rates, seed=seed)
+        dev, od, epp = env.device, env.obs_dim, self.envs_per_member
+        if env.n != P * epp:
+            raise ValueError(f"PopulationA2C: every member needs envs_per_member envs ({P} x {epp} != {env.n}: one "
+                             "batch for all members)")
+        del self.upd_m, self.upd_v            # (Adam's two of the parent: the state rows below take their place)
+        self.hyper, self.hyper_dev = table, table.to(dev)
+        self.learning_rates = table[:, A2C_HYPER_COLUMN["learning_rate"]].tolist()
+        for p, lr in enumerate(self.learning_rates):
+            self._lr[p] = lr
+        tf = table[:, A2C_HYPER_COLUMN["optimizer"]] == A2C_OPTIMIZERS.index("rmsprop_tf")
+        self.upd_s0 = tf.to(torch.float32)[:, None].expand(P, self.n_params).contiguous().to(dev)
+        self.upd_s1 = torch.zeros(P, self.n_params, dtype=torch.float32, device=dev)
+        self.stats = torch.zeros(P, 8, dtype=torch.float32, device=dev)
+        self.rows = self.member_rows(cfg.n_steps).contiguous()
+        per = int(self._L.b747_ppo_epoch_batched_workspace(od, max(2, cfg.n_steps * epp)))
+        if per <= 0:
+            raise ValueError(f"PopulationA2C: {self._L.b747_last_error().decode()}")
+        self.upd_ws_batched = torch.empty(max(1, min(P, self.BATCHED_WORKSPACE_CAP // per)) * per, dtype=torch.uint8,
+                                          device=dev)
+
+    @staticmethod
+    def _refuse(what: str, kw: dict):
+        """A2C draws no sample order and has one update path: the keywords PopulationPPO takes for those are refused"""
+        if kw:
+            raise ValueError(f"{what}: {sorted(kw)} not taken (A2C's one gradient step reads a member's whole rollout in "
+                             "order: there is no minibatch_order, sample_order or batched_update here)")
+
+    @property
+    def optimizers(self) -> list:
+        """Every member's optimiser by name (from the CPU table)"""
+        return [A2C_OPTIMIZERS[int(k)] for k in self.hyper[:, A2C_HYPER_COLUMN["optimizer"]].tolist()]
+
+    @torch.no_grad()
+    def _update(self, T: int):
+        """train()'s device work: one b747_a2c_update_population call on the first T * envs_per_member entries of every
+        member's row of `rows`, then the repack -- stream-ordered, no host read, allocation or synchronisation
+        (learn(use_graph=True) captures it)"""
+        c, p = self.cfg, _p
+        assert T <= c.n_steps
+        self._lib.check(self._L.b747_a2c_update_population(
+            p(self.flat), self.n_members, self.stride, self.env.obs_dim, p(self.obs_buf), p(self.act_buf),
+            p(self.adv_buf), p(self.ret_buf), p(self.rows), self.rows.shape[1], T * self.envs_per_member,
+            int(c.normalize_advantage), p(self.hyper_dev), p(self.upd_ws_batched), self.upd_ws_batched.numel(),
+            p(self.upd_s0), p(self.upd_s1), p(self.upd_t), c.rms_alpha, c.rms_eps, 0.9, 0.999, 1e-5, p(self.stats),
+            torch.cuda.current_stream().cuda_stream), "b747_a2c_update_population")
+        self.repack()
+
+    @torch.no_grad()
+    def _train_stats(self, T: int) -> dict:
+        """train()'s return value from `stats` and the rollout buffers: A2C.train's names as [P] tensors"""
+        P, epp = self.n_members, self.envs_per_member
+        st = self.stats.double()
+        v = self.val_buf[:T].reshape(T, P, epp).permute(1, 0, 2).reshape(P, -1)
+        r = self.ret_buf[:T].reshape(T, P, epp).permute(1, 0, 2).reshape(P, -1)
+        var_r = r.var(dim=1, unbiased=False)
+        ev = torch.where(var_r != 0, 1 - (r - v).var(dim=1, unbiased=False) / var_r, torch.full_like(var_r, float("nan")))
+        return {"policy_loss": st[:, 0], "value_loss": st[:, 1], "entropy_loss": st[:, 2], "loss": st[:, 7],
+                "explained_variance": ev, "std": self.flat[:, self.n_params - 1].exp(), "pg_term_scale": st[:, 5]}
+
+    def train(self, T: Optional[int] = None, **unsupported):
+        """A2C.train for every member: ONE b747_a2c_update_population call, then one b747_policy_pack_batch.  Returns
+        A2C.train's names as [P] tensors (the statistics float64 copies of `stats`; explained_variance and std
+        float32-derived), per member."""
+        self._refuse("PopulationA2C.train", unsupported)
+        T = T or self.cfg.n_steps
+        self._update(T)
+        return self._train_stats(T)
+
+    def _iteration(self, T: int):
+        """One iteration's device work: rollout, GAE, update, repack"""
+        self.collect_rollouts(T)
+        self.compute_gae(T)
+        self._update(T)
+
+    def _replay_iteration(self, T: int):
+        """_iteration as one replay of a HIP graph captured on one stream (a linear graph), captured when there is none
+        for this key (PopulationPPO._iteration_graph_key; the capture launches nothing: the first iteration is a replay
+        too).  The kernels read step_base, the table, the parameters and the optimiser state on the device when they run:
+        set_hyper and copy_member between replays are stream-ordered writes into buffers the graph already addresses."""
+        key = self._iteration_graph_key(T)
+        if self._graph is None or self._graph_key != key:
+            s = torch.cuda.Stream(device=self.env.device)
+            s.wait_stream(torch.cuda.current_stream())
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=s), torch.no_grad():
+                self._iteration(T)
+            self._graph, self._graph_key = g, key
+        self._graph.replay()
+
+    def learn(self, iterations: int, n_steps: Optional[int] = None, use_graph: bool = False, **unsupported):
+        """`iterations` x (collect_rollouts, compute_gae, train) after an env reset; train()'s values per iteration, with
+        mean_reward [P].  use_graph=True replays each iteration's device work as one HIP graph (_replay_iteration) and
+        reads the statistics outside it, from the persistent buffers; the same bits as use_graph=False.
+        self.control_test as PopulationPPO.learn's: its evaluations run before the iteration's device work, outside the
+        capture, and the entry gains the transfer_* values."""
+        self._refuse("PopulationA2C.learn", unsupported)
+        T, P, epp = n_steps or self.cfg.n_steps, self.n_members, self.envs_per_member
+        assert T <= self.cfg.n_steps
+        control_test = self.control_test
+        pushes = _control_test_plan(self, control_test, iterations, T)
+        self.env.reset()
+        hist = []
+        for it in range(iterations):
+            if pushes is not None and pushes[it]:
+                control_test.evaluate(pushes[it])
+            if use_graph:
+                self._replay_iteration(T)
+            else:
+                self._iteration(T)
+            st = self._train_stats(T)
+            st["mean_reward"] = self.rew_buf[:T].reshape(T, P, epp).mean(dim=(0, 2))
+            if pushes is not None:
+                st.update(control_test.history_entry())
+            hist.append(st)
+        return hist
+
+    def _fresh_state(self, p: int):
+        """Member p's optimiser state as a new optimiser object has it: stream-ordered fills"""
+        self.upd_s0[p].fill_(1.0 if self.optimizers[p] == "rmsprop_tf" else 0.0)
+        self.upd_s1[p].zero_()
+        self.upd_t[p].zero_()
+
+    def set_hyper(self, p: int, **kw):
+        """PopulationPPO.set_hyper for this class's keys (a2c_hyper_table's, validated the same way; nothing is written
+        before every value has passed).  Naming an `optimizer` other than the member's present one also re-initialises
+        that member's optimiser state and step count (upd_s0[p] ones for "rmsprop_tf", else zeros; upd_s1[p] and
+        upd_t[p] 0) with stream-ordered fills -- what a new optimiser object starts from."""
+        self._need_hyper("set_hyper", p)
+        unknown = sorted(set(kw) - set(A2C_HYPER_COLUMN))
+        if unknown:
+            raise ValueError(f"PopulationA2C.set_hyper: unknown key(s) {unknown}; a member's own values are "
+                             f"{sorted(A2C_HYPER_COLUMN)}")
+        new = {k: _check_a2c_hyper_value(k, x, f"PopulationA2C.set_hyper: member {p}") for k, x in kw.items()}
+        col = A2C_HYPER_COLUMN["optimizer"]
+        changed = "optimizer" in new and new["optimizer"] != float(self.hyper[p, col])
+        for k, x in new.items():
+            self.hyper[p, A2C_HYPER_COLUMN[k]] = x
+        self.learning_rates[p] = float(self.hyper[p, A2C_HYPER_COLUMN["learning_rate"]])
+        self._lr[p] = self.learning_rates[p]
+        self.hyper_dev[p].copy_(self.hyper[p], non_blocking=True)
+        if changed:
+            self._fresh_state(p)
+
+    def copy_member(self, src: int, dst: int, hyper: bool = True):
+        """PopulationPPO.copy_member with this class's state: member src's parameters (the whole stride of flat), both
+        optimiser state rows and the step count onto member dst, and with `hyper` its table row too (the optimiser kind
+        among its columns: without it the state rows are read by dst's own optimiser)."""
+        self._need_hyper("copy_member", src, dst)
+        if int(src) == int(dst):
+            return
+        for x in (self.flat, self.upd_s0, self.upd_s1, self.upd_t):
+            x[dst].copy_(x[src])
+        if hyper:
+            self.hyper[dst] = self.hyper[src]
+            self.learning_rates[dst] = self.learning_rates[src]
+            self._lr[dst] = self._lr[src]
+            self.hyper_dev[dst].copy_(self.hyper_dev[src])
+
+
 def control_test_pushes(iterations: int, T: int, log_interval: int) -> list:
     """How often iteration it = 0 .. iterations - 1 of T rollout steps makes the reference's ControlTestCallback fly
     its step tests: (it + 1) * T // L - it * T // L, the multiples of L = log_interval among the callback's n_calls

@@ -42,7 +42,7 @@ extern "C" {
                                 * b747_ppo_epoch_batched_workspace and b747_ppo_epoch_batched, then
                                 * b747_ppo_gae_population, b747_ppo_epoch_population_hyper and b747_ppo_epoch_batched_hyper,
                                 * then b747_ppo_sample_orders, then b747_ppo_track_best, then b747_a2c_grad,
-                                * b747_ppo_rmsprop and b747_a2c_update
+                                * b747_ppo_rmsprop and b747_a2c_update, then b747_a2c_update_population
                                 * came later as purely additive entry points under 15 (no struct, argument or
                                 * behaviour of an existing one changed): a library built before them still reports
                                 * 15, and a binding catches it by the missing entry point (_lib.bind) */
@@ -538,7 +538,7 @@ int32_t b747_ppo_epoch_batched(float *theta /* [n_policies][policy_stride] */, i
 #define B747_PPO_HYPER_VF_COEF 3
 #define B747_PPO_HYPER_MAX_GRAD_NORM 4
 #define B747_PPO_HYPER_GAMMA 5
-#define B747_PPO_HYPER_GAE_LAMBDA 6     /* (column 7: reserved) */
+#define B747_PPO_HYPER_GAE_LAMBDA 6     /* (column 7: reserved; b747_a2c_update_population's B747_PPO_HYPER_OPTIMIZER) */
 /* b747_ppo_epoch_population with member p's clip_range, ent_coef, vf_coef, max_grad_norm and lr taken from row p of
  * the HOST table hyper [n_policies][8] in place of the five arguments: the same host loop over the members of
  * b747_ppo_epoch's launches, each with its member's scalars as kernel arguments -- the bits of n_policies
@@ -701,6 +701,44 @@ int32_t b747_a2c_update(float *theta, int32_t obs_dim, const float *obs, const f
                         int32_t normalize_advantage, double ent_coef, double vf_coef, void *workspace, float *grad,
                         float *stats, int32_t optimizer, float *state0, float *state1 /* Adam's v, else may be NULL */,
                         int64_t *t, double max_grad_norm, double lr, double alpha, double eps, void *stream);
+
+/* ---- one A2C update of every member of a population (additive under ABI 15; ppo.PopulationA2C) ----
+ * b747_a2c_update for n_policies members at once: member p = blockIdx.y of member-batched siblings of its kernels
+ * (k_apop_adv_stats, k_apop_grad, k_apop_reduce, k_apop_opt) -- about four launches for the whole population in place
+ * of four per member.  Member p's parameters are theta + p * policy_stride; its minibatch is the rows
+ * rows[p * rows_stride + (0 .. batch)) of the time-major rollout buffers (an index table, device int64,
+ * [n_policies][rows_stride]: a member's rows t * N + p * envs_per_member + i are not a range; a prefix of a table row
+ * serves a shorter rollout, hence rows_stride >= batch); its ent_coef, vf_coef, max_grad_norm, lr and optimiser are
+ * columns B747_PPO_HYPER_ENT_COEF, _VF_COEF, _MAX_GRAD_NORM, _LR and _OPTIMIZER of row p of the DEVICE table hyper_dev
+ * [n_policies][B747_PPO_HYPER_COLS], read when the kernels run (see b747_ppo_epoch_batched_hyper; its values cannot be
+ * checked here); B747_PPO_HYPER_CLIP_RANGE, _GAMMA and _GAE_LAMBDA are not read.  Column B747_PPO_HYPER_OPTIMIZER holds
+ * a B747_OPT_* value as a double: 1 (B747_OPT_RMSPROP) and 2 (B747_OPT_RMSPROP_TF) run b747_ppo_rmsprop's arithmetic
+ * on state0[p] = sq with rms_alpha and rms_eps (a TF-like member's row starts at ONES, the caller's fill); ANY OTHER
+ * VALUE means Adam: b747_ppo_adam's arithmetic on state0[p] = m and state1[p] = v with adam_beta1, adam_beta2 and
+ * adam_eps.  Every kind adds 1 to t[p].  state0 and state1 are [n_policies][P] (P = the policy's parameter count; both
+ * required, whatever the members' optimisers), t [n_policies], stats [n_policies][8] in b747_a2c_grad's layout.
+ * normalize_advantage, the optimisers' alpha, betas and eps values are shared.  The PPO entry points keep ignoring
+ * column 7.
+ * workspace: one slice of b747_ppo_epoch_batched_workspace(obs_dim, batch) bytes per member (batch 1 takes batch 2's
+ * size); with fewer, the members run in chunks of min(n_policies, workspace_bytes / slice, 65535), which changes no bit.
+ * theta, state0, state1, t and stats get the bits of n_policies b747_a2c_update calls with idx = the member's table row
+ * and the member's scalars and optimiser.  -hipErrorInvalidValue before anything reaches the device (b747_last_error
+ * names the argument and this entry point) for a NULL pointer, an obs_dim without kernels, n_policies < 1, a
+ * policy_stride below the parameter count or not a multiple of 4, batch < 1 (< 2 with normalize_advantage),
+ * rows_stride < batch, workspace_bytes below one slice, rms_alpha, adam_beta1 or adam_beta2 outside [0, 1), or an eps
+ * that is not finite and above 0.  Stream-ordered, graph-capturable, allocates nothing, synchronises nothing, reads no
+ * per-member value on the host. */
+#define B747_PPO_HYPER_OPTIMIZER 7
+int32_t b747_a2c_update_population(float *theta /* [n_policies][policy_stride] */, int32_t n_policies,
+                                   int64_t policy_stride, int32_t obs_dim, const float *obs, const float *act,
+                                   const float *adv, const float *ret,
+                                   const int64_t *rows /* device, [n_policies][rows_stride] */, int64_t rows_stride,
+                                   int64_t batch, int32_t normalize_advantage,
+                                   const double *hyper_dev /* device, [n_policies][8] */, void *workspace,
+                                   int64_t workspace_bytes, float *state0, float *state1 /* [n_policies][P] */,
+                                   int64_t *t /* [n_policies] */, double rms_alpha, double rms_eps, double adam_beta1,
+                                   double adam_beta2, double adam_eps, float *stats /* [n_policies][8] */,
+                                   void *stream);
 
 /* Human-readable text of the last error returned on this thread. */
 const char *b747_last_error(void);
