@@ -10,6 +10,6 @@ from .ctrl_env import (BatchControllerEnv, CtrlMode, CtrlType, DisturbanceMode, 
                        ResetRefMode, RewardType)
 from .vec_env import B747GymVectorEnv, B747VecEnv, ep_rew_mean, make_vec_env  # noqa: F401
 from .storage import BatchStorage, Storage  # noqa: F401
-from .ppo import ControlTest, PopulationA2C  # noqa: F401
+from .ppo import ControlTest, PBT, PopulationA2C  # noqa: F401
 
 __version__ = "0.1.0"

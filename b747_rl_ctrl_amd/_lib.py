@@ -127,6 +127,10 @@ SIGNATURES = {
     #  adam_beta2, adam_eps, stats)
     "b747_a2c_update_population": ([_V, _I32, _I64, _I32] + [_V] * 5 + [_I64, _I64, _I32, _V, _V, _I64, _V, _V, _V]
                                    + [_F64] * 5 + [_V, _V], _I32),
+    # (exploit and explore for a population: score, n_members, n_replace, seed, step_base, round, params, stride, state0,
+    #  state1, n_state, upd_t, hyper, explore (a HOST array [8][4], may be None), rew, src_of)
+    "b747_ppo_exploit": ([_V, _I32, _I32, _U64, _V, _U32, _V, _I64, _V, _V, _I64, _V, _V, ctypes.POINTER(_F64), _V, _V, _V],
+                         _I32),
 }
 
 

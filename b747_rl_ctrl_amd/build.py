@@ -13,7 +13,8 @@ ARCH = os.environ.get("B747_OFFLOAD_ARCH", "gfx950")
 # csrc/b747_ppo_update.h, the GAE kernel, csrc/b747_ppo_gae.h, and the one-wave PPO rollout kernels,
 # csrc/b747_rollout_lanes.h, their population form, csrc/b747_rollout_population.h, and the sample-order kernel,
 # csrc/b747_ppo_order.h, the control-test bookkeeping kernel, csrc/b747_ppo_track.h, the A2C update,
-# csrc/b747_a2c_update.h, and its member-batched form, csrc/b747_a2c_population.h, likewise)
+# csrc/b747_a2c_update.h, its member-batched form, csrc/b747_a2c_population.h, and the exploit kernels,
+# csrc/b747_ppo_exploit.h, likewise)
 SOURCES = [os.path.join(HERE, "csrc", f) for f in ("b747_kernels.hip", "b747_fast.hip", "b747_eval_faithful.hip",
                                                    "b747_eval_fast.hip", "b747_ppo_update.hip",
                                                    "b747_ppo_gae.hip", "b747_rollout_lanes_faithful.hip",
@@ -21,7 +22,8 @@ SOURCES = [os.path.join(HERE, "csrc", f) for f in ("b747_kernels.hip", "b747_fas
                                                    "b747_rollout_population_faithful.hip",
                                                    "b747_rollout_population_fast.hip",
                                                    "b747_ppo_order.hip", "b747_ppo_track.hip",
-                                                   "b747_a2c_update.hip", "b747_a2c_population.hip")]
+                                                   "b747_a2c_update.hip", "b747_a2c_population.hip",
+                                                   "b747_ppo_exploit.hip")]
 DEPS = SOURCES + sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))
                         if f.endswith(".h")) + [os.path.join(ROOT, "include", "b747.h"),
                                                 os.path.join(ROOT, "include", "b747_tables.h"),

@@ -33,6 +33,7 @@
 #include "b747_ppo_gae.h"
 #include "b747_ppo_order.h"
 #include "b747_ppo_track.h"
+#include "b747_ppo_exploit.h"
 
 using namespace b747;
 
@@ -636,6 +637,41 @@ B747_API int32_t b747_ppo_track_best(const double *eval_out, int64_t n_eval, con
     const TrackArgs a{eval_out, vref, params, ring, count, last, window_mean, best_quality, best_eval, best_params,
                       n_eval, stride, tk, n_members, envs_per_policy, n_refs, window, repeat};
     return launched(W, launch_ppo_track_best(a, (hipStream_t)stream));
+}
+
+B747_API int32_t b747_ppo_exploit(const double *score, int32_t n_members, int32_t n_replace, uint64_t seed,
+                                  const uint64_t *step_base, uint32_t round, float *params, int64_t stride,
+                                  float *state0, float *state1, int64_t n_state, int64_t *upd_t, double *hyper,
+                                  const double *explore, double *rew, int32_t *src_of, void *stream)
+{
+    const char *const W = "b747_ppo_exploit";
+    if (int32_t e = check_not_null(W, {{score, "score"}, {params, "params"}, {state0, "state0"}, {state1, "state1"},
+                                       {upd_t, "upd_t"}, {src_of, "src_of"}}))
+        return e;
+    if (n_members < 2 || n_members > kExploitMaxMembers)
+        return bad_arg(W, "n_members (outside [2, 4096]: one workgroup ranks the scores in LDS)");
+    if (n_replace < 1 || n_replace > n_members / 2)
+        return bad_arg(W, "n_replace (outside [1, n_members / 2]: winners and losers must be disjoint)");
+    if (stride < 4 || stride % 4 != 0)
+        return bad_arg(W, "stride (at least 4 floats and a multiple of 4: a parameter row is copied 16 bytes at a time)");
+    if (n_state < 1) return bad_arg(W, "n_state < 1");
+    if (explore && !hyper) return bad_arg(W, "explore without hyper (there is no table to perturb)");
+    ExploitArgs a{};
+    a.score = score; a.step_base = step_base; a.params = params; a.state0 = state0; a.state1 = state1; a.upd_t = upd_t;
+    a.hyper = hyper; a.rew = rew; a.src_of = src_of; a.stride = stride; a.n_state = n_state; a.seed = seed;
+    a.round = round; a.n_members = n_members; a.n_replace = n_replace; a.has_explore = explore ? 1 : 0;
+    for (int j = 0; j < kExploitCols; ++j) {
+        // (a host array, read here; without one the factors are 1 and the bounds open, which the kernel does not read)
+        const double f_lo = explore ? explore[4 * j] : 1.0, f_hi = explore ? explore[4 * j + 1] : 1.0;
+        const double lo = explore ? explore[4 * j + 2] : -INFINITY, hi = explore ? explore[4 * j + 3] : INFINITY;
+        if (!isfinite(f_lo) || !isfinite(f_hi) || !(f_lo > 0.0) || !(f_hi > 0.0))
+            return bad_arg(W, "explore (a factor that is not finite and above 0)");
+        if (f_lo > f_hi) return bad_arg(W, "explore (f_lo > f_hi)");
+        if (lo != lo || hi != hi) return bad_arg(W, "explore (a bound is NaN)");
+        if (lo > hi) return bad_arg(W, "explore (min > max)");
+        a.explore[j][0] = f_lo; a.explore[j][1] = f_hi; a.explore[j][2] = lo; a.explore[j][3] = hi;
+    }
+    return launched(W, launch_ppo_exploit(a, (hipStream_t)stream));
 }
 
 B747_API int32_t b747_ppo_epoch(float *theta, int32_t obs_dim, const float *obs, const float *act, const float *old_logp,

@@ -216,6 +216,59 @@ def _check_hyper_value(key: str, x, where: str) -> float:
     return x
 
 
+# The default exploration rule of PopulationPPO.exploit: key -> (f_lo, f_hi, min, max).  The factors
+# 0.8 / 1.2 are the convention of the population-based-training paper (Jaderberg et al., 2017), not a measured choice;
+# the bounds are the reference's PPO trial ranges (neural/setups.py, trial_hyperparams).  Keys not named are copied.
+PBT_EXPLORE = {"learning_rate": (0.8, 1.2, 1e-5, 1e-3), "ent_coef": (0.8, 1.2, 0.0, 0.01)}
+# (PopulationA2C's: the reference's A2C trial ranges)
+A2C_PBT_EXPLORE = {"learning_rate": (0.8, 1.2, 1e-5, 1.0), "ent_coef": (0.8, 1.2, 1e-8, 0.1)}
+
+
+def explore_table(columns: dict, check, explore: dict, where: str) -> list:
+    """b747_ppo_exploit's `explore` argument from a dict key -> (f_lo, f_hi, min, max) over the keys of `columns`
+    (HYPER_COLUMN or A2C_HYPER_COLUMN): HYPER_COLS rows of four floats, a column that is not named an identity row
+    (factors 1, bounds -inf / +inf: an exact copy).  ValueError for an unknown key, for `optimizer` (a kind, not a
+    magnitude: it can only be copied), for factors that are not finite with 0 < f_lo <= f_hi, for a bound outside the
+    key's own domain (`check`: _check_hyper_value or _check_a2c_hyper_value) and for min > max."""
+    rows = [[1.0, 1.0, -math.inf, math.inf] for _ in range(HYPER_COLS)]
+    unknown = sorted(set(explore) - set(columns))
+    if unknown:
+        raise ValueError(f"{where}: explore: unknown key(s) {unknown}; a member's own values are {sorted(columns)}")
+    if "optimizer" in explore:
+        raise ValueError(f"{where}: explore: optimizer cannot be perturbed (it names a kind; it is copied with the row)")
+    for key, spec in explore.items():
+        if len(spec) != 4:
+            raise ValueError(f"{where}: explore[{key!r}] takes (f_lo, f_hi, min, max)")
+        f_lo, f_hi, lo, hi = (float(x) for x in spec)
+        if not (math.isfinite(f_lo) and math.isfinite(f_hi) and 0.0 < f_lo <= f_hi):
+            raise ValueError(f"{where}: explore[{key!r}]: factors ({f_lo}, {f_hi}) are not finite with 0 < f_lo <= f_hi")
+        lo, hi = check(key, lo, f"{where}: explore[{key!r}] min"), check(key, hi, f"{where}: explore[{key!r}] max")
+        if lo > hi:
+            raise ValueError(f"{where}: explore[{key!r}]: min {lo} > max {hi}")
+        rows[columns[key]] = [f_lo, f_hi, lo, hi]
+    return rows
+
+
+class PBT:
+    """The settings of a population-based schedule (truncation selection), attached to a population as
+    `pop.pbt = PBT(interval)`: learn() then calls pop.exploit(fraction=, explore=, rewards=) before the device work of
+    every iteration it > 0 with it % interval == 0, ranking the members by `score`: "transfer_quality" (the attached
+    ControlTest's windowed quality, optimize()'s objective; the step is skipped until a first evaluation exists) or
+    "mean_reward" (the previous iteration's per-member mean reward as float64; needs no control test).  A plain
+    settings object: it holds no device state."""
+
+    SCORES = ("transfer_quality", "mean_reward")
+
+    def __init__(self, interval: int, fraction: float = 0.25, explore=None, rewards: bool = False,
+                 score: str = "transfer_quality"):
+        if int(interval) != interval or int(interval) < 1:
+            raise ValueError(f"PBT: interval={interval!r} (a whole number of iterations, at least 1)")
+        if score not in self.SCORES:
+            raise ValueError(f"PBT: score={score!r}: one of {list(self.SCORES)}")
+        self.interval, self.fraction, self.explore = int(interval), float(fraction), explore
+        self.rewards, self.score = bool(rewards), score
+
+
 def hyper_table(cfg: PPOConfig, n_members: int, hyper=None, learning_rates=None) -> torch.Tensor:
     """The [n_members, 8] float64 CPU table of per-member hyper-parameters (columns HYPER_COLUMN, the last one 0).
     hyper: None or one dict per member with keys among learning_rate, clip_range, ent_coef, vf_coef, max_grad_norm,
@@ -914,7 +967,11 @@ class PopulationPPO:
     not the default's ("host": torch's generator, today's calls and bits) and train() takes no minibatch_order hook.  A
     member's rows are limited to 16,384 (n_steps * envs_per_member; the kernel sorts them in LDS).  With it no host
     randomness is left in an iteration, and learn(use_graph=True) replays rollout, GAE, the epochs and the repack as one
-    HIP graph per iteration (with batched_update=True, whose calls read every per-member value on the device)."""
+    HIP graph per iteration (with batched_update=True, whose calls read every per-member value on the device).
+
+    exploit() is the exploit-and-explore step of a population-based schedule done on the device by one
+    b747_ppo_exploit call -- the worst members by a device score re-seeded from the best, with perturbed table rows, no
+    host read -- and `pop.pbt = PBT(interval)` makes learn() take that step every `interval` iterations."""
 
     # The batched update's workspace holds one slice per member (b747_ppo_epoch_batched_workspace: ~9 MB at the full
     # 256-workgroup grid, ~80 kB at batch 256) so that all members run in one launch; past this many bytes the call
@@ -939,6 +996,8 @@ class PopulationPPO:
         self.sample_order = sample_order
         self._graph, self._graph_key = None, None
         self.control_test = None          # a ControlTest that learn() flies and books before every iteration
+        self.pbt = None                   # a PBT whose exploit steps learn() makes between iterations
+        self._exploits, self._hyper_stale = 0, False
         if sample_order == "device":
             # the persistent order buffer, and the first draw into it (epoch 0 at step_base 0; train() draws again): the
             # entry point refuses a member of more rows than it sorts, or envs that the members do not cover, before
@@ -989,8 +1048,9 @@ class PopulationPPO:
         if sample_order == "device":      # (persistent: a captured iteration writes it, the reductions read it afterwards)
             self.stats = z(self.cfg.n_epochs * P * -(-T * epp // self.cfg.batch_size) * 8)
         self.step_base = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.src_of = torch.arange(P, dtype=torch.int32, device=dev)      # exploit()'s result, persistent
         self.act_lo, self.act_hi = float(env.action_space.low), float(env.action_space.high)
-        if self._rollout(0) != 0:                         # T = 0: validates the configuration, launches nothing
+        if self._rollout(0) != 0:                        # T = 0: validates the configuration, launches nothing
             raise ValueError(f"b747_ppo_rollout_population does not cover this env: {self._L.b747_last_error().decode()}")
 
     def _rollout(self, T: int) -> int:
@@ -1189,11 +1249,13 @@ class PopulationPPO:
             raise ValueError("PopulationPPO.learn: minibatch_order with sample_order=\"device\" (the orders are "
                              "b747_ppo_sample_orders')")
         assert T <= self.cfg.n_steps
+        self._pbt_check()
         self.env.reset()
         hist = []
         for it in range(iterations):
             if pushes is not None and pushes[it]:
                 control_test.evaluate(pushes[it])
+            source = self._pbt_step(it, hist)
             if use_graph:
                 st = self._train_stats(T, self._replay_iteration(T))
             else:
@@ -1203,8 +1265,135 @@ class PopulationPPO:
             st["mean_reward"] = self.rew_buf[:T].reshape(T, P, epp).mean(dim=(0, 2))
             if pushes is not None:
                 st.update(control_test.history_entry())
+            if source is not None:
+                st["pbt_source"] = source
             hist.append(st)
         return hist
+
+    # ------------------------------------------------------------------ exploit and explore --
+    _HYPER_KEYS = HYPER_COLUMN
+    _check_value = staticmethod(_check_hyper_value)
+    PBT_EXPLORE = PBT_EXPLORE
+
+    def _table_on_device(self) -> bool:
+        """Whether the update reads the hyper-parameter table on the device (the batched epoch call does; the other one
+        reads the HOST table, which a device step cannot update)"""
+        return bool(self.batched_update)
+
+    def _state_rows(self):
+        """The two optimiser state buffers [P, n_params] that travel with a member (Adam's m and v)"""
+        return self.upd_m, self.upd_v
+
+    def _exploit_args(self, fraction, explore, rewards):
+        """exploit()'s host-side checks, all before any device work: (n_replace, the explore rows or None)"""
+        name, P = type(self).__name__, self.n_members
+        if self.hyper is not None and not self._table_on_device():
+            raise ValueError(f"{name}.exploit needs batched_update=True (the other epoch call reads the "
+                             "hyper-parameter table on the host, which a step on the device cannot update)")
+        n_replace = int(P * float(fraction))
+        if not 1 <= n_replace <= P // 2:
+            raise ValueError(f"{name}.exploit: fraction={fraction} replaces {n_replace} of {P} members (at least 1, at "
+                             f"most {P // 2}: winners and losers must be disjoint)")
+        if self.hyper is None:
+            if explore is not None:
+                raise ValueError(f"{name}.exploit: explore on a population built with hyper=None (it has no table: it "
+                                 "exploits parameters and optimiser state only)")
+            rows = None
+        else:
+            rule = self.PBT_EXPLORE if explore is None else dict(explore)
+            rows = explore_table(self._HYPER_KEYS, self._check_value, rule, f"{name}.exploit") if rule else None
+        if rewards and self._rew_arg is None:
+            raise ValueError(f"{name}.exploit: rewards=True on a population built without rew_configs (its rollout "
+                             "kernel reads no per-member reward constants)")
+        return n_replace, rows
+
+    @torch.no_grad()
+    def exploit(self, score=None, fraction: float = 0.25, explore=None, rewards: bool = False, round=None):
+        """The exploit-and-explore step of a truncation-selection population-based schedule (Jaderberg et al., 2017),
+        decided and done on the device by one b747_ppo_exploit call (include/b747.h states the contract):
+        the n_replace = int(P * fraction) worst members by `score` are each re-seeded from one of the n_replace best,
+        drawn at random (a counter-based stream keyed by seed, step_base, `round` and the member), if that one is
+        strictly better.  A replaced member takes its source's parameters (the whole stride of flat), optimiser state
+        rows, step count and table row, the row's columns perturbed by `explore`.  No host read, no synchronisation.
+
+        score: a [P] float64 device tensor, higher is better, NaN ranks last; default self.control_test.objective(),
+        the windowed transfer quality (ValueError without a control test or before its first evaluation -- the host's
+        count of them).  explore: a dict key -> (f_lo, f_hi, min, max) over the class's hyper keys: the copied value
+        times f_lo or f_hi (a fair coin per column), clamped to [min, max]; keys not named are copied unchanged, {}
+        copies every column; default PBT_EXPLORE (learning_rate and ent_coef at 0.8 / 1.2 -- the paper's convention,
+        not a measured choice -- inside the reference's trial ranges).  A population built with hyper=None takes no
+        explore.  rewards=True also moves the source's reward constants (`rew`; needs rew_configs); by default a
+        member's reward constants are its own.  round: default the number of exploit calls so far.
+        With a table PopulationPPO needs batched_update=True.  An attached control test's window books (ring, count,
+        last, window_mean) follow the policy; best_quality, best_eval and best_flat stay the slot's own.  Afterwards
+        the CPU mirrors (hyper, learning_rates) are stale until sync_hyper().
+        Returns src_of, [P] int32, a persistent device buffer: src_of[p] = the member p was replaced from, or p."""
+        n_replace, rows = self._exploit_args(fraction, explore, rewards)
+        name, P, p = type(self).__name__, self.n_members, _p
+        ct = self.control_test
+        if score is None:
+            if ct is None:
+                raise ValueError(f"{name}.exploit: no score and no control test (attach one, or pass score=)")
+            if ct.evaluations == 0:
+                raise ValueError(f"{name}.exploit: the control test has not evaluated yet (its objective is NaN)")
+            score = ct.objective()
+        if not (isinstance(score, torch.Tensor) and score.dtype == torch.float64 and tuple(score.shape) == (P,)
+                and score.device == self.flat.device):
+            raise ValueError(f"{name}.exploit: score is a [{P}] float64 tensor on {self.flat.device}")
+        score = score.contiguous()
+        arr = None if rows is None else (ctypes.c_double * (4 * HYPER_COLS))(*[x for row in rows for x in row])
+        s0, s1 = self._state_rows()
+        self._lib.check(self._L.b747_ppo_exploit(
+            p(score), P, n_replace, self.seed & 0xFFFFFFFFFFFFFFFF, p(self.step_base),
+            (self._exploits if round is None else int(round)) & 0xFFFFFFFF, p(self.flat), self.stride, p(s0), p(s1),
+            self.n_params, p(self.upd_t), None if self.hyper is None else p(self.hyper_dev), arr,
+            p(self.rew) if rewards else None, p(self.src_of), torch.cuda.current_stream().cuda_stream),
+            "b747_ppo_exploit")
+        self._exploits += 1
+        self._hyper_stale = self.hyper is not None
+        if ct is not None:          # (small: torch gathers on the stream)
+            idx = self.src_of.long()
+            ct.ring.copy_(ct.ring[:, idx])
+            for x in (ct.count, ct.last, ct.window_mean):
+                x.copy_(x[idx])
+        return self.src_of
+
+    def sync_hyper(self):
+        """Bring the CPU mirrors (hyper, learning_rates) up to date with hyper_dev after a device exploit: one
+        device-to-host copy -- a HOST READ, the only one of this feature; set_hyper, copy_member and
+        PopulationA2C.optimizers make it when the mirror is stale, nothing else does."""
+        if self.hyper is not None:
+            self.hyper.copy_(self.hyper_dev)
+            for p, lr in enumerate(self.hyper[:, 0].tolist()):        # (column 0: learning_rate, in both key sets)
+                self.learning_rates[p] = lr
+                self._lr[p] = lr
+        self._hyper_stale = False
+
+    def _pbt_check(self):
+        """learn()'s checks of self.pbt before any device work"""
+        pbt = getattr(self, "pbt", None)
+        if pbt is None:
+            return
+        self._exploit_args(pbt.fraction, pbt.explore, pbt.rewards)
+        if pbt.score == "transfer_quality" and self.control_test is None:
+            raise ValueError(f"{type(self).__name__}.learn: pbt ranks by transfer_quality, which needs a control test "
+                             "(attach one, or use PBT(score=\"mean_reward\"))")
+
+    def _pbt_step(self, it: int, hist: list):
+        """The exploit step learn() makes before iteration `it`'s device work where self.pbt asks for one and a score
+        exists; the iteration's pbt_source entry (a [P] int32 device clone of src_of, arange(P) where no exploit ran),
+        or None without a pbt"""
+        pbt = getattr(self, "pbt", None)
+        if pbt is None:
+            return None
+        if it > 0 and it % pbt.interval == 0:
+            if pbt.score == "mean_reward":
+                score = hist[-1]["mean_reward"].double()
+            else:
+                score = None if self.control_test.evaluations > 0 else False
+            if score is not False:
+                return self.exploit(score, pbt.fraction, pbt.explore, pbt.rewards).clone()
+        return torch.arange(self.n_members, dtype=torch.int32, device=self.flat.device)
 
     def _need_hyper(self, what: str, *members):
         if self.hyper is None:
@@ -1220,6 +1409,8 @@ class PopulationPPO:
         No buffer is rebuilt, and a captured graph of the population's calls stays valid (the kernels read the table
         when they run)."""
         self._need_hyper("set_hyper", p)
+        if getattr(self, "_hyper_stale", False):
+            self.sync_hyper()
         unknown = sorted(set(kw) - set(HYPER_COLUMN))
         if unknown:
             raise ValueError(f"PopulationPPO.set_hyper: unknown key(s) {unknown}; a member's own values are "
@@ -1237,6 +1428,8 @@ class PopulationPPO:
         synchronisation -- the exploit step of a population-based schedule, and what optimize()'s "keep the best"
         needs.  The members' envs, reward constants and rollout rows stay their own."""
         self._need_hyper("copy_member", src, dst)
+        if getattr(self, "_hyper_stale", False):
+            self.sync_hyper()
         if int(src) == int(dst):
             return
         for x in (self.flat, self.upd_m, self.upd_v, self.upd_t):
@@ -1379,7 +1572,10 @@ class PopulationA2C(PopulationPPO):
 
     @property
     def optimizers(self) -> list:
-        """Every member's optimiser by name (from the CPU table)"""
+        """Every member's optimiser by name (from the CPU table, brought up to date first after a device exploit:
+        sync_hyper, a host read)"""
+        if getattr(self, "_hyper_stale", False):
+            self.sync_hyper()
         return [A2C_OPTIMIZERS[int(k)] for k in self.hyper[:, A2C_HYPER_COLUMN["optimizer"]].tolist()]
 
     @torch.no_grad()
@@ -1450,11 +1646,13 @@ class PopulationA2C(PopulationPPO):
         assert T <= self.cfg.n_steps
         control_test = self.control_test
         pushes = _control_test_plan(self, control_test, iterations, T)
+        self._pbt_check()
         self.env.reset()
         hist = []
         for it in range(iterations):
             if pushes is not None and pushes[it]:
                 control_test.evaluate(pushes[it])
+            source = self._pbt_step(it, hist)
             if use_graph:
                 self._replay_iteration(T)
             else:
@@ -1463,8 +1661,22 @@ class PopulationA2C(PopulationPPO):
             st["mean_reward"] = self.rew_buf[:T].reshape(T, P, epp).mean(dim=(0, 2))
             if pushes is not None:
                 st.update(control_test.history_entry())
+            if source is not None:
+                st["pbt_source"] = source
             hist.append(st)
         return hist
+
+    # (exploit and explore: this class's key set and state rows; its update always reads the table on the device)
+    _HYPER_KEYS = A2C_HYPER_COLUMN
+    _check_value = staticmethod(_check_a2c_hyper_value)
+    PBT_EXPLORE = A2C_PBT_EXPLORE
+
+    def _table_on_device(self) -> bool:
+        return True
+
+    def _state_rows(self):
+        """The two optimiser state rows (upd_s0, upd_s1): they travel together with the optimiser column"""
+        return self.upd_s0, self.upd_s1
 
     def _fresh_state(self, p: int):
         """Member p's optimiser state as a new optimiser object has it: stream-ordered fills"""
@@ -1478,6 +1690,8 @@ class PopulationA2C(PopulationPPO):
         that member's optimiser state and step count (upd_s0[p] ones for "rmsprop_tf", else zeros; upd_s1[p] and
         upd_t[p] 0) with stream-ordered fills -- what a new optimiser object starts from."""
         self._need_hyper("set_hyper", p)
+        if getattr(self, "_hyper_stale", False):
+            self.sync_hyper()
         unknown = sorted(set(kw) - set(A2C_HYPER_COLUMN))
         if unknown:
             raise ValueError(f"PopulationA2C.set_hyper: unknown key(s) {unknown}; a member's own values are "
@@ -1498,6 +1712,8 @@ class PopulationA2C(PopulationPPO):
         optimiser state rows and the step count onto member dst, and with `hyper` its table row too (the optimiser kind
         among its columns: without it the state rows are read by dst's own optimiser)."""
         self._need_hyper("copy_member", src, dst)
+        if getattr(self, "_hyper_stale", False):
+            self.sync_hyper()
         if int(src) == int(dst):
             return
         for x in (self.flat, self.upd_s0, self.upd_s1, self.upd_t):

@@ -42,7 +42,8 @@ extern "C" {
                                 * b747_ppo_epoch_batched_workspace and b747_ppo_epoch_batched, then
                                 * b747_ppo_gae_population, b747_ppo_epoch_population_hyper and b747_ppo_epoch_batched_hyper,
                                 * then b747_ppo_sample_orders, then b747_ppo_track_best, then b747_a2c_grad,
-                                * b747_ppo_rmsprop and b747_a2c_update, then b747_a2c_update_population
+                                * b747_ppo_rmsprop and b747_a2c_update, then b747_a2c_update_population, then
+                                * b747_ppo_exploit
                                 * came later as purely additive entry points under 15 (no struct, argument or
                                 * behaviour of an existing one changed): a library built before them still reports
                                 * 15, and a binding catches it by the missing entry point (_lib.bind) */
@@ -739,6 +740,69 @@ int32_t b747_a2c_update_population(float *theta /* [n_policies][policy_stride] *
                                    int64_t *t /* [n_policies] */, double rms_alpha, double rms_eps, double adam_beta1,
                                    double adam_beta2, double adam_eps, float *stats /* [n_policies][8] */,
                                    void *stream);
+
+/* ---- exploit and explore for a population, on the device (additive under ABI 15; DESIGN.md 22;
+ * PopulationPPO.exploit, ppo.PBT) ----
+ * The step of a truncation-selection population-based schedule (Jaderberg et al., 2017): the n_replace worst members
+ * by `score` are each re-seeded from one of the n_replace best, drawn at random, and take its parameters, optimiser
+ * state and -- perturbed -- its row of the hyper-parameter table.  Decided and done on the device; nothing is read back.
+ * All pointers are device memory except `explore`.
+ *
+ * Order.  s'(p) = score[p], a NaN read as -inf.  Member q is BETTER than p when s'(q) > s'(p), or s'(q) == s'(p) and
+ * q < p (IEEE comparisons: -0.0 == +0.0).  rank(p) = the number of members better than p: a total order, every rank
+ * 0 .. n_members - 1 taken once.  WINNERS have rank < n_replace, LOSERS rank >= n_members - n_replace;
+ * n_replace <= n_members / 2 keeps the two sets disjoint, so a source row is never written and the step runs in place.
+ *
+ * Draw.  Loser p takes ONE Philox4x32-10 block (the rounds of the reset draws, the action noise and
+ * b747_ppo_sample_orders) with
+ *   sb  = step_base ? *step_base : 0                          (read on the device, when the kernel runs)
+ *   K   = (seed ^ 0x6578706C6F697431) ^ ((sb >> 32) * 0x9E3779B97F4A7C15),   key (lo32(K), hi32(K))
+ *   ctr = (p, 0, lo32(sb), round)
+ * The tag ("exploit1") keeps the stream apart from the action noise and the sample orders; `round` tells the exploit
+ * steps of one step_base apart.  Word 0 picks the source: q = the winner of rank w = (uint64(word0) * n_replace) >> 32.
+ * Bit j of word 1 picks column j's factor: 0 gives f_lo, 1 gives f_hi.
+ *
+ * Decision.  Loser p with source q is REPLACED only if s'(q) > s'(p), strictly: a population of equal or all-NaN
+ * scores changes nothing, and a NaN member is never a source.  src_of[p] = q where p is replaced and src_of[p] = p for
+ * every other member (winners, the middle, losers that were not replaced); all n_members entries are written by every
+ * call.
+ *
+ * A replaced member p receives from q:
+ *   params[p][0 .. stride)           the whole stride, so the packed sections travel (16-byte loads and stores; rows
+ *                                    16-byte aligned)
+ *   state0[p], state1[p]             [0 .. n_state) each (4-byte elements: n_state is odd for the product's policies,
+ *                                    so the rows of two members differ in 16-byte phase; no alignment is assumed)
+ *   upd_t[p]
+ *   rew[p][0 .. 8)                   if rew is given ([n_members][8] doubles: b747_ppo_rollout_population's rew_pop)
+ *   hyper[p][0 .. 8)                 if hyper is given ([n_members][B747_PPO_HYPER_COLS]).  Without `explore` an exact
+ *                                    copy.  With it, in float64, column j becomes
+ *                                      fmin(fmax(hyper[q][j] * f, min_j), max_j),   explore[j] = (f_lo, f_hi, min, max)
+ *                                    -- one multiply (not contracted), two selects; C's fmax / fmin: a NaN product
+ *                                    gives min_j.  A column with factors 1 and bounds -inf / +inf is an exact copy
+ *                                    (b747_a2c_update_population's optimiser column is passed as such a column).
+ * No row of any other member is touched, in any buffer.
+ *
+ * explore is a HOST array [B747_PPO_HYPER_COLS][4], read and validated before the call returns (as
+ * b747_ppo_epoch_population's learning rates) and passed to the kernel by value: a capture holds a fixed exploration
+ * rule.  step_base may be NULL (0).  hyper may be NULL; then explore must be NULL too.  explore may be NULL with a
+ * table: rows then travel unchanged.  rew may be NULL.
+ *
+ * -hipErrorInvalidValue before anything reaches the device (b747_last_error names this entry point and the argument)
+ * for a NULL score, params, state0, state1, upd_t or src_of; n_members outside [2, 4096] (one workgroup ranks the
+ * members: 8 bytes of score and two 16-bit tables each in static LDS); n_replace outside [1, n_members / 2]; stride < 4
+ * or not a multiple of 4; n_state < 1; explore without hyper; an explore row with a factor that is not finite and above
+ * 0, f_lo > f_hi, a NaN bound, or min > max.
+ * Two launches (k_exploit_plan: one workgroup; k_exploit_copy: a grid of (chunks, n_members) workgroups, those of a
+ * member that is not replaced returning at once).  Stream-ordered, graph-capturable, allocates nothing, synchronises
+ * nothing, reads nothing back, no atomics: the same inputs give the same bits. */
+int32_t b747_ppo_exploit(const double *score /* device, [n_members] */, int32_t n_members, int32_t n_replace,
+                         uint64_t seed, const uint64_t *step_base /* device, nullable: 0 */, uint32_t round,
+                         float *params /* device, [n_members][stride] */, int64_t stride,
+                         float *state0, float *state1 /* device, [n_members][n_state] */, int64_t n_state,
+                         int64_t *upd_t /* device, [n_members] */, double *hyper /* device, [n_members][8], nullable */,
+                         const double *explore /* HOST, [8][4], nullable */,
+                         double *rew /* device, [n_members][8], nullable */, int32_t *src_of /* device, [n_members] */,
+                         void *stream);
 
 /* Human-readable text of the last error returned on this thread. */
 const char *b747_last_error(void);
